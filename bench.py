@@ -28,7 +28,17 @@ carries the same job timed on ONE of the GPUs (``single_gpu_same_workload``) so 
 off one line.  A single filter (configs[1], [3]) does not shard - that would need a cross-GPU scan - so
 ``--workload apf_lgo_1m`` etc. with N > 1 run one replica per GPU (weak scaling) and all-gather the log-likelihoods.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. ``roofline`` and ``cpu_baseline``.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times ``--steps`` passes and
+prints the line; ``ms_per_step`` is the wall time of one timed pass.  Everything else moves behind ``--full``: the step kernel's
+``roofline`` (an instrumented pass, the device copy ceiling, the rocprofv3 PMC passes), the ``cpu_baseline``, the check of the
+log-likelihood against the oracle's value (``loglikelihood_check``), and the extra SMC^2 records (the one-GPU leg of a multi-GPU
+line, ``smc2_scaling`` at N > 1).  Without ``--full`` ``roofline`` and ``cpu_baseline`` are null.
+
+``--dump-outputs DIR`` writes what the timed path handed its caller in the last timed pass as ``DIR/<name>.npy`` (float32 /
+float64; rank 0): the filter result (log-likelihoods, filter means / variances, the final particles, log-weights and ancestors),
+or for ``smc2`` the theta-particles, their log-weights and the posterior mean.  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.  At most 48 MiB are written; a larger array is replaced by a fixed, seeded
+sample of its flattened elements (``dump_outputs``).
 """
 import argparse
 import json
@@ -80,7 +90,8 @@ def check_loglikelihood(workload, w, ll_all):
 
 
 def run_smc2(w, dtype, device, world, rank, steps, warmup, t_override=None, solo=False):
-    """BASELINE configs[4] as the algorithm; returns (elapsed seconds for `steps` full fits, info).  ``solo``: the whole
+    """BASELINE configs[4] as the algorithm; returns (elapsed seconds for `steps` full fits, info, the last fit's outputs for
+    ``--dump-outputs``).  ``solo``: the whole
     job (``w["B"]`` theta-particles) on this rank alone, no sharding, no collectives (the single-GPU reference leg of a
     multi-GPU line).  ``w["B"]`` is the TOTAL number of theta-particles: 1 024 (strong scaling) or 1 024 per GPU (weak)."""
     import torch.distributed as dist
@@ -129,10 +140,15 @@ def run_smc2(w, dtype, device, world, rank, steps, warmup, t_override=None, solo
         alg, state = fit(100 + k)
     barrier()
     elapsed = time.perf_counter() - t0
+    posterior_mean = alg.posterior_mean(state)
     info = {"rejuvenations": len(alg._kernel.acceptance_history), "particle_increases": alg._kernel._increases,
-            "state_particles_at_end": int(alg.filter.particles[0]), "posterior_mean": alg.posterior_mean(state).tolist(),
+            "state_particles_at_end": int(alg.filter.particles[0]), "posterior_mean": posterior_mean.tolist(),
             "theta_per_rank": alg.shard.local, "T": t_len, "block": alg._block}
-    return elapsed, info, state.global_weights()
+    # what the caller of the last fit receives (all ranks take part in the gathers; rank 0 writes them)
+    theta = alg.theta.stack_parameters(True)
+    outputs = {"theta_log_weights": state.global_weights(), "theta_parameters": alg.shard.all_gather(theta) if alg.shard.collective else theta,
+               "posterior_mean": posterior_mean}
+    return elapsed, info, outputs
 
 
 
@@ -241,13 +257,15 @@ def smc2_line(args, dtype, device, world, rank, scaling, attach=False):
     per_gpu = w["B"]
     if scaling == "weak":
         w["B"] = per_gpu * world
-    elapsed, info, _ = run_smc2(w, dtype, device, world, rank, args.steps, args.warmup, args.T)
+    elapsed, info, outputs = run_smc2(w, dtype, device, world, rank, args.steps, args.warmup, args.T)
+    if rank == 0 and args.dump_outputs and not attach:
+        dump_outputs(args.dump_outputs, outputs)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
     solo = None
-    if world > 1:  # the one-GPU job of the same curve on ONE of these GPUs (rank 0 alone, the others wait)
+    if world > 1 and args.full:  # the one-GPU job of the same curve on ONE of these GPUs (rank 0 alone, the others wait)
         if rank == 0:
             try:  # (rank 0 alone: whatever happens here it must reach the barrier the others wait at)
                 k = max(1, min(2, args.steps))
@@ -260,7 +278,7 @@ def smc2_line(args, dtype, device, world, rank, scaling, attach=False):
                 solo = {"error": f"{type(exc).__name__}: {exc}"}
         dist.barrier()
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             roof = smc2_step_kernel_roofline(w, info["theta_per_rank"], dtype, device)
         except Exception as exc:
@@ -273,7 +291,7 @@ def smc2_line(args, dtype, device, world, rank, scaling, attach=False):
     if solo and "value" in solo:
         solo["speedup_over_it"] = value / solo["value"]
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not attach:
+    if world == 1 and args.full and not args.no_cpu_baseline and not attach:
         cpu = smc2_cpu_baseline(dict(w, T=info["T"]))
     out = {
         "metric": f"particle-steps/sec (batch x particles x T), SMC^2 {w['B']} theta x {w['N']} particles", "value": value,
@@ -549,6 +567,56 @@ def pmc_traffic(kernel_substr, workload, dtype_name, t_len=20, n_override=None):
                     "by the per-XCD L2 (the whole working set of this workload fits in L2 + Infinity Cache) do not appear"}
 
 
+def result_line(args, w, world, value, elapsed, ll_all):
+    """The JSON line of a filter workload as a plain run prints it (``--full`` fills ``roofline`` / ``cpu_baseline`` and adds
+    ``config.loglikelihood_check``)."""
+    return {
+        "metric": "particle-steps/sec (batch x particles x T), 1M-particle APF",
+        "value": value,
+        "unit": "particle-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic",
+        "world_size": world,
+        "rccl_version": _rccl_version(world),
+        "config": {
+            "workload": f"{args.workload}: {w['filter'].upper()} + {w['proposal']} proposal, {w['resampler']} "
+                        f"resampling, N={w['N']} particles x B={w['B']} filters per GPU, T={w['T']}, state dim {w['D']}",
+            "ms_per_filter_step": 1e3 * elapsed / args.steps / w["T"],
+            "parallelism": "independent filters per GPU + all-gather of log-likelihoods" if world > 1 else "single GPU",
+            "loglikelihood_sample": float(ll_all.reshape(-1)[0]),
+        },
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+
+
+def dump_outputs(outdir, arrays, limit=48 << 20):
+    """``DIR/<name>.npy`` for every tensor of ``arrays``: floating types as float32 / float64, integers as float64 (exact below
+    2^53).  The ``limit`` bytes are shared equally between the arrays; an array above its share is replaced by a fixed sample
+    of its flattened elements (a seeded permutation, kept in index order), so a dump stays within the limit at every workload
+    size and two runs pick the same elements."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()
+        flat = t.reshape(-1)
+        cap = share // flat.element_size()
+        if flat.numel() > cap:
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = flat[pick.to(flat.device)]
+        np.save(os.path.join(outdir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -563,11 +631,18 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--T", type=int, default=None, help="override the number of observations")
     ap.add_argument("--N", type=int, default=None, help="override the number of particles (development: shape studies)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes that fill roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check what the headline does not need: roofline, CPU baseline, the oracle check of the "
+                         "log-likelihood, the extra SMC^2 records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass returned to its caller as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 PMC passes that fill roofline.traffic")
     ap.add_argument("--_inner", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--direct", action="store_true", help=argparse.SUPPRESS)  # (A/B: every run through the direct driver)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.direct:
         from pyfilter_amd.hints import HINTS
 
@@ -674,14 +749,25 @@ def main():
 
     units_per_pass = w["N"] * w["B"] * w["T"] * world
     value = units_per_pass * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        state = res.latest_state
+        outputs = {"loglikelihood": res.loglikelihood, "filter_means": res.filter_means, "filter_variance": res.filter_variance,
+                   "particles": state.timeseries_state.value, "log_weights": state.weights, "ancestors": state.previous_indices}
+        if world > 1:
+            outputs["loglikelihood_all_ranks"] = ll_all
+        dump_outputs(args.dump_outputs, outputs)
+    if args._inner or not args.full:  # (the profiled child of pmc_traffic(): the timed passes above are all it needs)
+        if rank == 0 and not args._inner:
+            print(json.dumps(result_line(args, w, world, value, elapsed, ll_all)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     ll_check = check_loglikelihood(args.workload, w, ll_all)  # (raises: no throughput line for a wrong answer)
 
     if args.direct:
         from pyfilter_amd.hints import HINTS
 
         HINTS.direct = True
-    if args._inner:  # profiled child of pmc_traffic(): the timed passes above are all it needs
-        return
 
     # ---- the step kernel's duration: HIP events on the launch stream around the T launches of an instrumented pass ----
     filt._time_kernels = True
@@ -733,32 +819,9 @@ def main():
         cpu = None
         if not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.workload, w)
-        out = {
-            "metric": "particle-steps/sec (batch x particles x T), 1M-particle APF",
-            "value": value,
-            "unit": "particle-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "world_size": world,
-            "rccl_version": _rccl_version(world),
-            "config": {
-                "workload": f"{args.workload}: {w['filter'].upper()} + {w['proposal']} proposal, {w['resampler']} "
-                            f"resampling, N={w['N']} particles x B={w['B']} filters per GPU, T={w['T']}, state dim {w['D']}",
-                "ms_per_filter_step": 1e3 * elapsed / args.steps / w["T"],
-                "parallelism": "independent filters per GPU + all-gather of log-likelihoods" if world > 1 else "single GPU",
-                "loglikelihood_sample": float(ll_all.reshape(-1)[0]),
-                "loglikelihood_check": ll_check,
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
+        out = result_line(args, w, world, value, elapsed, ll_all)
+        out["config"]["loglikelihood_check"] = ll_check
+        out.update(roofline=roofline, cpu_baseline=cpu)
         if cpu:
             out["speedup_vs_cpu_baseline"] = value / cpu["value"]
     if world > 1 and default_job and not args.no_smc2:

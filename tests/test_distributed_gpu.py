@@ -103,7 +103,8 @@ def test_bench_spawns_its_own_ranks_one_workload_at_every_n():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PF_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--T", "24", "--N", "65536"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--T", "24", "--N", "65536",
+           "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -128,13 +129,46 @@ def test_bench_smc2_is_one_workload_from_one_gpu_on():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "smc2", "--steps", "1", "--warmup", "1", "--T", "40"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "smc2", "--steps", "1", "--warmup", "1", "--T", "40",
+           "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert rec["n_gpus"] == 1 and rec["scaling"] == "strong" and rec["config"]["theta_per_rank"] == 1024
     assert rec["roofline"]["kernel"] == "k_fused_step" and 0 < rec["roofline"]["frac"] < 1.5
     assert rec["cpu_baseline"]["kind"] == "port" and rec["cpu_baseline"]["value"] > 0 and rec["speedup_vs_cpu_baseline"] > 1
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1`` run (no ``--full``): the headline line only - ``steps`` timed passes, ``ms_per_step`` per
+    pass, no roofline / CPU baseline / oracle check - and ``--dump-outputs`` writes the last timed pass's filter result."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--T", "24", "--N", "65536",
+           "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+    assert rec["value"] > 0 and rec["unit"] == "particle-steps/s" and rec["higher_is_better"] is True
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and "loglikelihood_check" not in rec["config"]
+    got = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(got) == {"loglikelihood", "filter_means", "filter_variance", "particles", "log_weights", "ancestors"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert float(got["loglikelihood"]) == rec["config"]["loglikelihood_sample"]
+    assert got["particles"].shape == got["log_weights"].shape == got["ancestors"].shape == (65536,)
+    assert got["filter_means"].shape[0] == 25 and np.isfinite(got["filter_means"]).all() and np.isfinite(got["particles"]).all()
+    anc = got["ancestors"]
+    assert (anc == np.round(anc)).all() and anc.min() >= 0 and anc.max() < 65536
 
 
 def _rccl_worker(rank, world, port, out):
@@ -193,7 +227,8 @@ def test_bench_smc2_over_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n = min(torch.cuda.device_count(), 8)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PF_BENCH_SHARE_GPU")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--T", "60"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--T", "60",
+                          "--full"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

@@ -575,3 +575,22 @@ def test_moment_log_remembers_single_rows_and_writes_them_when_somebody_looks(ma
     assert torch.equal(log.means(), torch.stack([m for m, _ in ref]))
     assert torch.equal(log.variances(), torch.stack([v for _, v in ref]))
 
+
+
+def test_bench_dump_outputs_types_sizes_and_a_fixed_sample(tmp_path):
+    """``bench.py --dump-outputs``: every array lands as ``<name>.npy`` in float32 / float64 (integers exactly, as float64),
+    small arrays whole, an array above its share of the byte limit as the same seeded sample on every call."""
+    import bench
+
+    big = torch.arange(1 << 20, dtype=torch.float32)
+    arrays = {"ll": torch.tensor(-3.5, dtype=torch.float64), "anc": torch.tensor([0, 5, 1 << 20]), "x": big}
+    limit = 3 * 4 * 1000  # 4 000 bytes per array: 1 000 float32 elements of `x`
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=limit)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["ll"].dtype == np.float64 and a["ll"].shape == () and a["ll"] == -3.5
+    assert a["anc"].dtype == np.float64 and a["anc"].tolist() == [0.0, 5.0, float(1 << 20)]
+    x = a["x"]
+    assert x.dtype == np.float32 and x.shape == (1000,) and len(np.unique(x)) == 1000 and (np.diff(x) > 0).all()
+    assert np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in arrays) <= limit + 3 * 128  # (+ the .npy headers)

@@ -30,7 +30,7 @@ b = os.path.join(src, "bench_smc2.json")
 if os.path.exists(b) and os.path.getsize(b):
     lines.append(open(b).read().strip())
 with open(os.path.join(dst, f"{tag}_bench.json.log"), "w") as f:
-    f.write(f"# {tag} {note}: python bench.py --workload <w>  (one JSON line per workload; the first is the headline)\n")
+    f.write(f"# {tag} {note}: python bench.py --workload <w> --full  (one JSON line per workload; the first is the headline)\n")
     f.write("\n".join(lines) + "\n")
 for ln in lines:
     d = json.loads(ln)

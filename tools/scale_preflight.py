@@ -44,7 +44,7 @@ def _bench(extra, timeout):
 
 def check_smc2_line(quick):
     t_args = ["--T", "40"] if quick else []
-    rec, wall = _bench(["--gpus", "2", "--workload", "smc2", "--steps", "1", "--warmup", "1", "--no-traffic", "--no-cpu-baseline"] + t_args,
+    rec, wall = _bench(["--gpus", "2", "--workload", "smc2", "--steps", "1", "--warmup", "1", "--full", "--no-traffic", "--no-cpu-baseline"] + t_args,
                        1800)
     missing = [k for k in CONTRACT if k not in rec]
     assert not missing, f"keys missing from the line: {missing}"
@@ -61,7 +61,7 @@ def check_smc2_line(quick):
 
 def check_default_line(quick):
     t_args = ["--T", "24", "--N", "65536"] if quick else []
-    rec, _ = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-traffic"] + t_args, 2400)
+    rec, _ = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-traffic"] + t_args, 2400)
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["config"]["workload"].startswith("apf_lgo_1m")
     assert rec["rccl_version"] is None and rec["roofline"]["frac"] > 0
     strong, weak = rec["smc2_scaling"]["strong"], rec["smc2_scaling"]["weak"]
