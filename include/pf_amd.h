@@ -57,6 +57,13 @@ extern "C" {
                               * particle, so loc(x[anc]) = loc(x)[anc] - and do everything else (ancestors, gather, draws, Bootstrap
                               * or the optimal linear-Gaussian proposal, weights, moments, log-likelihood) as for a built-in
                               * kind.  One step per pf_filter_run call (the next step's planes need the new particles). */
+#define PF_HID_LINEAR_MAT 6  /* loc = b + A x with a full D x D matrix A,  scale = s (constant per column), 1 <= D <= 8, under
+                              * PF_OBS_LINEAR with 1 <= O <= 8 (stochproc LinearModel, the reference's tests/filters/models.py:28-38).
+                              * Its parameter row is NOT the hp layout below:
+                              *   [ A[D x D] row-major | b[D] | s[D] | A_obs[O x D] row-major | b_obs[O] | s_obs[O] ]
+                              *   NP = D*D + 2*D + O*D + 2*O
+                              * Stand-alone model kernels only (pf_sample_and_weight, pf_pre_weight): pf_filter_run and
+                              * pf_smooth_ffbs refuse it (PF_EUNSUPPORTED). */
 /* observation kinds */
 #define PF_OBS_LINEAR 0 /* y ~ N(b + A x, s)   (LinearStateSpaceModel; proposals/linear.py:48) */
 #define PF_OBS_SV 1     /* y ~ N(mu, scale = x)                                                 */
@@ -81,7 +88,8 @@ typedef struct pf_model {
     double dt;
     double inc_scale; /* 1 for the discrete kinds, sqrt(dt) for Euler-Maruyama */
     /* (B, NP) parameter rows, dtype = the call's dtype, NP = 4*D + O*D + 2*O, one row per column:
-     *   [ hp0[D] hp1[D] hp2[D] hp3[D] | A[O x D] row-major | b[O] | s[O] ]   (PF_OBS_SV: b[0] = mu) */
+     *   [ hp0[D] hp1[D] hp2[D] hp3[D] | A[O x D] row-major | b[O] | s[O] ]   (PF_OBS_SV: b[0] = mu)
+     * PF_HID_LINEAR_MAT: [ A[D x D] | b[D] | s[D] | A_obs[O x D] | b_obs[O] | s_obs[O] ], NP = D*D + 2*D + O*D + 2*O */
     const void* params;
 } pf_model;
 
@@ -92,7 +100,8 @@ int pf_abi_version(void);
 const char* pf_error_string(int code);
 
 /* Scratch bytes any call below needs for an (N, B, D) problem - an upper bound over every tile geometry a call may be
- * given (pf_run_hints.tile_target), so a workspace of this size serves all of them. */
+ * given (pf_run_hints.tile_target), so a workspace of this size serves all of them.  Any D >= 1: the stand-alone
+ * primitives handle the planes of a larger state in groups of three, the size does not grow with D. */
 int pf_workspace_bytes(int64_t N, int64_t B, int64_t D, size_t* bytes);
 
 /* ------------------------------------------------------------------------------------------------------------ *
@@ -155,7 +164,7 @@ int pf_columns_exchange(void* dst, const void* src, const uint8_t* mask, int64_t
 int pf_loglik(const void* v, const void* W, void* out, int64_t N, int64_t B, int dtype, void* ws, size_t ws_bytes,
               void* stream);
 
-/* get_filter_mean_and_variance (particle/utils.py:26-65), covariance=False: mean (B,D), var (B,D). */
+/* get_filter_mean_and_variance (particle/utils.py:26-65), covariance=False: mean (B,D), var (B,D).  Any D >= 1. */
 int pf_moments(const void* x, const void* W, void* mean, void* var, int64_t N, int64_t B, int64_t D, int dtype,
                void* ws, size_t ws_bytes, void* stream);
 
@@ -172,7 +181,8 @@ int pf_sample_and_weight(const pf_model* model, int proposal, int weigh, const v
                          int64_t y_rows, const void* z, uint64_t seed, uint32_t step, void* x_out, void* w_out,
                          int64_t N, int64_t B, int dtype, void* stream);
 
-/* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles. */
+/* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
+ * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
 int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                       int64_t B, int64_t D, int dtype, void* stream);
 

@@ -15,13 +15,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpfamd.so")
 
 PF_F32, PF_F64 = 0, 1
-HID_LINEAR, HID_SINE_EM, HID_VERHULST_EM, HID_LORENZ63_EM, HID_OU, HID_USER_AFFINE = 0, 1, 2, 3, 4, 5
+HID_LINEAR, HID_SINE_EM, HID_VERHULST_EM, HID_LORENZ63_EM, HID_OU, HID_USER_AFFINE, HID_LINEAR_MAT = 0, 1, 2, 3, 4, 5, 6
 OBS_LINEAR, OBS_SV = 0, 1
 PROP_BOOTSTRAP, PROP_LGO = 0, 1
 FILTER_SISR, FILTER_APF = 0, 1
 RESAMPLE_SYSTEMATIC, RESAMPLE_MULTINOMIAL = 0, 1
-MAX_D = 3
+MAX_D = 3  # the fused / column / cluster kernels (PF_MAXD, PF_MAXO)
 MAX_O = 3
+LIN_MAX_D = 8  # PF_HID_LINEAR_MAT on the stand-alone model kernels (pf_linear.hpp)
+LIN_MAX_O = 8
 
 EXPORTS = (
     "pf_version", "pf_abi_version", "pf_error_string", "pf_workspace_bytes", "pf_normalize", "pf_systematic", "pf_systematic_cdf_free", "pf_systematic_logw",
@@ -200,8 +202,8 @@ def workspace(n: int, b: int, device: torch.device) -> torch.Tensor:
     key = (n, b, device.index, stream_ptr())
     ws = _ws_cache.get(key)
     nbytes = C.c_size_t(0)
-    if ws is None:  # (the size is a bound over every tile geometry: include/pf_amd.h)
-        check(load().pf_workspace_bytes(n, b, MAX_D, C.byref(nbytes)), "pf_workspace_bytes")
+    if ws is None:  # (the size is a bound over every tile geometry and any state dimension: include/pf_amd.h)
+        check(load().pf_workspace_bytes(n, b, 1, C.byref(nbytes)), "pf_workspace_bytes")
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
         if len(_ws_cache) > 64:
             _ws_cache.clear()

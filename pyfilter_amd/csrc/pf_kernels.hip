@@ -21,6 +21,7 @@
 #include "pf_device.hpp"
 #include "pf_models.hpp"
 #include "pf_philox.hpp"
+#include "pf_linear.hpp"
 
 namespace pf {
 
@@ -1373,9 +1374,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_moments_part(const T* __restrict__
     }
 }
 
+// (D here: the planes of this launch, <= PF_MAXD; pf_moments launches once per group of PF_MAXD planes and the row of a column
+// in mean / var is `ld` long, the group's first plane at `d0`)
 template <typename T>
 __global__ __launch_bounds__(PF_BLOCK) void k_moments_final(const double* __restrict__ part, T* __restrict__ mean,
-                                                            T* __restrict__ var, Geom g, int D) {
+                                                            T* __restrict__ var, Geom g, int D, int d0, int ld) {
     __shared__ double red[(1 + 2 * PF_MAXD) * PF_NWAVES];
     const int b = blockIdx.x;
     const int64_t stride = (int64_t)g.B * g.tiles;
@@ -1390,8 +1393,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_moments_final(const double* __rest
         for (int d = 0; d < D; ++d) {
             const double mu = acc[1 + d];  // sum W x  (the reference does not divide by sum W)
             const double v = acc[1 + PF_MAXD + d] - 2.0 * mu * acc[1 + d] + mu * mu * acc[0];
-            mean[(int64_t)b * D + d] = (T)mu;
-            var[(int64_t)b * D + d] = (T)(v < 0.0 ? 0.0 : v);
+            mean[(int64_t)b * ld + d0 + d] = (T)mu;
+            var[(int64_t)b * ld + d0 + d] = (T)(v < 0.0 ? 0.0 : v);
         }
     }
 }
@@ -1457,11 +1460,11 @@ template <typename T>
 __global__ __launch_bounds__(PF_BLOCK) void k_initial_sample(double m0a, double m0b, double m0c, double s0a,
                                                              double s0b, double s0c, const T* __restrict__ z,
                                                              uint64_t seed, T* __restrict__ x, int64_t N, int B,
-                                                             int D) {
+                                                             int D, uint32_t group) {
     const int b = blockIdx.y;
     for (int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * PF_BLOCK) {
         T zv[4] = {T(0), T(0), T(0), T(0)};
-        if (!z) NormalDraw<T, 4>::draw(seed, PF_STREAM_INIT, 0u, (uint64_t)((int64_t)b * N + i), zv);
+        if (!z) NormalDraw<T, 4>::draw(seed, PF_STREAM_INIT, group, (uint64_t)((int64_t)b * N + i), zv);
 #pragma unroll
         for (int d = 0; d < PF_MAXD; ++d) {
             if (d < D) {
@@ -1477,11 +1480,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_initial_sample(double m0a, double 
 template <typename T>
 __global__ __launch_bounds__(PF_BLOCK) void k_initial_sample_cols(const T* __restrict__ m0, int64_t mb, int64_t md, const T* __restrict__ s0,
                                                                   int64_t sb, int64_t sd, const T* __restrict__ z, uint64_t seed,
-                                                                  T* __restrict__ x, int64_t N, int B, int D) {
+                                                                  T* __restrict__ x, int64_t N, int B, int D, uint32_t group) {
     const int b = blockIdx.y;
     for (int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * PF_BLOCK) {
         T zv[4] = {T(0), T(0), T(0), T(0)};
-        if (!z) NormalDraw<T, 4>::draw(seed, PF_STREAM_INIT, 0u, (uint64_t)((int64_t)b * N + i), zv);
+        if (!z) NormalDraw<T, 4>::draw(seed, PF_STREAM_INIT, group, (uint64_t)((int64_t)b * N + i), zv);
 #pragma unroll
         for (int d = 0; d < PF_MAXD; ++d) {
             if (d < D) {
@@ -1688,6 +1691,11 @@ static inline bool bad_shape(int64_t N, int64_t B) { return N < 1 || B < 1 || N 
 static inline int check_model(const pf_model* m, bool fused = false) {
     if (!m || !m->params) return PF_EINVAL;
     if (m->hid_kind == PF_HID_USER_AFFINE && !fused) return PF_EUNSUPPORTED;
+    if (m->hid_kind == PF_HID_LINEAR_MAT) {  // the stand-alone model kernels only (pf_linear.hpp): no fused / column route
+        if (fused || m->dim < 1 || m->dim > PF_LIN_MAXD || m->obs_dim < 1 || m->obs_dim > PF_LIN_MAXO || m->obs_kind != PF_OBS_LINEAR)
+            return PF_EUNSUPPORTED;
+        return PF_OK;
+    }
     if (m->dim < 1 || m->dim > PF_MAXD || m->obs_dim < 1 || m->obs_dim > PF_MAXO) return PF_EUNSUPPORTED;
     if (m->dim == 1 && m->obs_dim != 1) return PF_EUNSUPPORTED;
     if (m->hid_kind < 0 || m->hid_kind > PF_HID_USER_AFFINE) return PF_EUNSUPPORTED;
@@ -1758,8 +1766,9 @@ extern "C" int pf_debug_offset(int64_t N, int64_t B, size_t* off) {
 }
 #endif
 
+// (any D: pf_moments reduces the planes in groups of PF_MAXD, so the stand-alone primitives need no more than a PF_MAXD problem)
 extern "C" int pf_workspace_bytes(int64_t N, int64_t B, int64_t D, size_t* bytes) {
-    if (!bytes || bad_shape(N, B) || D < 1 || D > PF_MAXD) return PF_EINVAL;
+    if (!bytes || bad_shape(N, B) || D < 1) return PF_EINVAL;
     *bytes = ws_bound(N, B, PF_MAXD);
     return PF_OK;
 }
@@ -1963,21 +1972,29 @@ extern "C" int pf_loglik(const void* v, const void* W, void* out, int64_t N, int
 
 extern "C" int pf_moments(const void* x, const void* W, void* mean, void* var, int64_t N, int64_t B, int64_t D,
                           int dtype, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !W || !mean || !var || !ws || bad_shape(N, B) || D < 1 || D > PF_MAXD) return PF_EINVAL;
+    if (!x || !W || !mean || !var || !ws || bad_shape(N, B) || D < 1) return PF_EINVAL;
+    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
     const Geom g = make_geom(N, B);
     const WsLayout wl = make_ws(g, PF_MAXD);
     if (ws_bytes < wl.total) return PF_EWORKSPACE;
     double* part = (double*)((char*)ws + wl.off_part);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(g.tiles, g.B);
-    if (dtype == PF_F32) {
-        hipLaunchKernelGGL((k_moments_part<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)x, (const float*)W, part, g, (int)D);
-        hipLaunchKernelGGL((k_moments_final<float>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (float*)mean, (float*)var, g, (int)D);
-    } else if (dtype == PF_F64) {
-        hipLaunchKernelGGL((k_moments_part<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)x, (const double*)W, part, g, (int)D);
-        hipLaunchKernelGGL((k_moments_final<double>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (double*)mean, (double*)var, g, (int)D);
-    } else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
+    // the planes in groups of PF_MAXD (one pair of launches per group, the same partial slots reused in stream order)
+    const int64_t plane = N * B;
+    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+        if (dtype == PF_F32) {
+            hipLaunchKernelGGL((k_moments_part<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)x + d0 * plane, (const float*)W, part, g, dg);
+            hipLaunchKernelGGL((k_moments_final<float>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (float*)mean, (float*)var, g,
+                               dg, (int)d0, (int)D);
+        } else {
+            hipLaunchKernelGGL((k_moments_part<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)x + d0 * plane, (const double*)W, part, g, dg);
+            hipLaunchKernelGGL((k_moments_final<double>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (double*)mean, (double*)var, g,
+                               dg, (int)d0, (int)D);
+        }
+        PF_CHECK_LAUNCH();
+    }
     return PF_OK;
 }
 
@@ -1990,6 +2007,17 @@ extern "C" int pf_moments(const void* x, const void* W, void* mean, void* var, i
         if (D == 1) { CALL(double, 1) } else if (D == 2) { CALL(double, 2) } else { CALL(double, 3) }   \
     } else return PF_EINVAL;
 
+// PF_HID_LINEAR_MAT: the state dimension as a template argument, 1 .. 8 (check_model bounds it)
+#define PF_DISPATCH_D8(T, D, CALL)                                                                                  \
+    switch (D) {                                                                                                    \
+        case 1: { CALL(T, 1) } break; case 2: { CALL(T, 2) } break; case 3: { CALL(T, 3) } break;                    \
+        case 4: { CALL(T, 4) } break; case 5: { CALL(T, 5) } break; case 6: { CALL(T, 6) } break;                    \
+        case 7: { CALL(T, 7) } break; case 8: { CALL(T, 8) } break; default: return PF_EUNSUPPORTED;                  \
+    }
+#define PF_DISPATCH_T_D8(dtype, D, CALL)                                                                            \
+    if (dtype == PF_F32) { PF_DISPATCH_D8(float, D, CALL) } else if (dtype == PF_F64) { PF_DISPATCH_D8(double, D, CALL) } \
+    else return PF_EINVAL;
+
 extern "C" int pf_pre_weight(const pf_model* model, int proposal, const void* x, const void* y, int64_t y_rows,
                              void* out, int64_t N, int64_t B, int dtype, void* stream) {
     int rc = check_model(model);
@@ -1999,6 +2027,15 @@ extern "C" int pf_pre_weight(const pf_model* model, int proposal, const void* x,
     const ModelDesc md = to_desc(model);
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
+    if (model->hid_kind == PF_HID_LINEAR_MAT) {
+#define CALL(T, DD)                                                                                                                  \
+    hipLaunchKernelGGL((k_linmat_pre_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params, (int)model->obs_dim, proposal, \
+                       (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
+        PF_DISPATCH_T_D8(dtype, model->dim, CALL)
+#undef CALL
+        PF_CHECK_LAUNCH();
+        return PF_OK;
+    }
 #define CALL(T, DD)                                                                                                  \
     hipLaunchKernelGGL((k_pre_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, proposal,    \
                        (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
@@ -2018,6 +2055,15 @@ extern "C" int pf_sample_and_weight(const pf_model* model, int proposal, int wei
     const ModelDesc md = to_desc(model);
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
+    if (model->hid_kind == PF_HID_LINEAR_MAT) {
+#define CALL(T, DD)                                                                                                                  \
+    hipLaunchKernelGGL((k_linmat_sample_and_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params, (int)model->obs_dim,      \
+                       proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step, (T*)x_out, (T*)w_out, N, (int)B);
+        PF_DISPATCH_T_D8(dtype, model->dim, CALL)
+#undef CALL
+        PF_CHECK_LAUNCH();
+        return PF_OK;
+    }
 #define CALL(T, DD)                                                                                                  \
     hipLaunchKernelGGL((k_sample_and_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params,       \
                        proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step, (T*)x_out,   \
@@ -2030,17 +2076,25 @@ extern "C" int pf_sample_and_weight(const pf_model* model, int proposal, int wei
 
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
-    if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1 || D > PF_MAXD) return PF_EINVAL;
-    double m[3] = {0, 0, 0}, s[3] = {0, 0, 0};
-    for (int d = 0; d < D; ++d) { m[d] = m0[d]; s[d] = s0[d]; }
+    if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;
+    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_initial_sample<float>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2], (const float*)z, seed, (float*)x, N, (int)B, (int)D);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_initial_sample<double>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2], (const double*)z, seed, (double*)x, N, (int)B, (int)D);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
+    // planes in groups of PF_MAXD; group k draws its Philox normals at step k (group 0: the draws of a D <= 3 state)
+    const int64_t plane = N * B;
+    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+        double m[3] = {0, 0, 0}, s[3] = {0, 0, 0};
+        for (int d = 0; d < dg; ++d) { m[d] = m0[d0 + d]; s[d] = s0[d0 + d]; }
+        const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
+        if (dtype == PF_F32)
+            hipLaunchKernelGGL((k_initial_sample<float>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2],
+                               z ? (const float*)z + d0 * plane : nullptr, seed, (float*)x + d0 * plane, N, (int)B, dg, grp);
+        else
+            hipLaunchKernelGGL((k_initial_sample<double>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2],
+                               z ? (const double*)z + d0 * plane : nullptr, seed, (double*)x + d0 * plane, N, (int)B, dg, grp);
+        PF_CHECK_LAUNCH();
+    }
     return PF_OK;
 }
 
@@ -2048,19 +2102,27 @@ extern "C" int pf_initial_sample(const double* m0, const double* s0, const void*
 extern "C" int pf_initial_sample_cols(const void* m0, int64_t m0_stride_b, int64_t m0_stride_d, const void* s0, int64_t s0_stride_b,
                                       int64_t s0_stride_d, const void* z, uint64_t seed, void* x, int64_t N, int64_t B, int64_t D,
                                       int dtype, void* stream) {
-    if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1 || D > PF_MAXD || m0_stride_b < 0 || m0_stride_d < 0 || s0_stride_b < 0 ||
+    if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1 || m0_stride_b < 0 || m0_stride_d < 0 || s0_stride_b < 0 ||
         s0_stride_d < 0)
         return PF_EINVAL;
+    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_initial_sample_cols<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)m0, m0_stride_b, m0_stride_d,
-                           (const float*)s0, s0_stride_b, s0_stride_d, (const float*)z, seed, (float*)x, N, (int)B, (int)D);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_initial_sample_cols<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)m0, m0_stride_b, m0_stride_d,
-                           (const double*)s0, s0_stride_b, s0_stride_d, (const double*)z, seed, (double*)x, N, (int)B, (int)D);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
+    // (the plane groups of pf_initial_sample, the same draws)
+    const int64_t plane = N * B;
+    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+        const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
+        if (dtype == PF_F32)
+            hipLaunchKernelGGL((k_initial_sample_cols<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)m0 + d0 * m0_stride_d, m0_stride_b,
+                               m0_stride_d, (const float*)s0 + d0 * s0_stride_d, s0_stride_b, s0_stride_d,
+                               z ? (const float*)z + d0 * plane : nullptr, seed, (float*)x + d0 * plane, N, (int)B, dg, grp);
+        else
+            hipLaunchKernelGGL((k_initial_sample_cols<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)m0 + d0 * m0_stride_d, m0_stride_b,
+                               m0_stride_d, (const double*)s0 + d0 * s0_stride_d, s0_stride_b, s0_stride_d,
+                               z ? (const double*)z + d0 * plane : nullptr, seed, (double*)x + d0 * plane, N, (int)B, dg, grp);
+        PF_CHECK_LAUNCH();
+    }
     return PF_OK;
 }
 
@@ -2219,7 +2281,7 @@ extern "C" int pf_theta_ess(const void* logw, int64_t rows, int64_t B, int dtype
 // ---- smoothing ---------------------------------------------------------------------------------------------------------
 extern "C" int pf_smooth_fixed_lag(const void* x_hist, const int32_t* anc_hist, void* out, int64_t S, int64_t N, int64_t B,
                                    int64_t D, int dtype, void* stream) {
-    if (!x_hist || !anc_hist || !out || S < 1 || bad_shape(N, B) || D < 1 || D > PF_MAXD) return PF_EINVAL;
+    if (!x_hist || !anc_hist || !out || S < 1 || bad_shape(N, B) || D < 1) return PF_EINVAL;  // (any D: the planes are looped)
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == PF_F32)
@@ -2237,6 +2299,7 @@ extern "C" int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const v
     if (!model || !x_hist || !logw_hist || !x_last || !out || S < 1 || bad_shape(N, B)) return PF_EINVAL;
     int rc = check_model(model);
     if (rc) return rc;
+    if (model->hid_kind == PF_HID_LINEAR_MAT) return PF_EUNSUPPORTED;  // (the callers' torch-logits route: no k_ffbs of this kind)
     const ModelDesc md = to_desc(model);
     const dim3 grid((unsigned)((N + PF_BLOCK - 1) / PF_BLOCK), (int)B);
     hipStream_t st = (hipStream_t)stream;

@@ -299,6 +299,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             device.type == "cuda"
             and self._FILTER_KIND is not None
             and self._kernel_kind() is not None
+            and self._kernel_kind().fused  # (PF_HID_LINEAR_MAT, D > 3, O > 3: step by step on the stand-alone model kernels)
             and type(self._proposal) in (Bootstrap, LinearGaussianObservations)
             and not self._proposal._custom_pre_weight
             and self._resampler_kind() is not None
@@ -1017,7 +1018,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
 
         start = batched_gather(x_last, idx, 0)
         ctx = self._ensure_context()
-        if ctx is not None and on_gpu and not ctx.kind.is_user:
+        if ctx is not None and on_gpu and not ctx.kind.is_user and ctx.kind.hid_kind != L.HID_LINEAR_MAT:
             x_hist, w_hist, _ = self._history(states)
             u = getattr(self, "_ffbs_u", None)
             if u is not None:

@@ -74,6 +74,14 @@ class KernelKind:
         self.obs_dim = None
 
     @property
+    def fused(self) -> bool:
+        """Whether the fused one-launch kernels (pf_filter_run: the fused step, column and cluster kernels) implement this kind.
+        They hold states of up to ``MAX_D`` components observed through up to ``MAX_O``; ``PF_HID_LINEAR_MAT`` and any larger
+        shape run step by step on the stand-alone model kernels."""
+        return (self.hid_kind != L.HID_LINEAR_MAT and self.dim <= L.MAX_D
+                and (self.obs_dim is None or self.obs_dim <= L.MAX_O))
+
+    @property
     def is_user(self) -> bool:
         """A user-defined affine process: its ``mean_scale`` callable is evaluated with PyTorch-ROCm ops once per step and
         handed to the fused kernels as (loc, scale) planes (``PF_HID_USER_AFFINE``)."""
@@ -308,10 +316,12 @@ class LinearStateSpaceModel(StateSpaceModel):
             hk = _user_affine_kind(hidden)
         if hk is not None:
             o = obs_event.numel() if len(obs_event) else 1
-            if hk.dim <= L.MAX_D and o <= L.MAX_O and (hk.dim > 1 or o == 1):
+            max_d, max_o = (L.LIN_MAX_D, L.LIN_MAX_O) if hk.hid_kind == L.HID_LINEAR_MAT else (L.MAX_D, L.MAX_O)
+            if hk.dim <= max_d and o <= max_o and (hk.dim > 1 or o == 1):
                 kind = KernelKind(hk.hid_kind, hk.dim, hk.dt, hk.inc_scale)
                 kind.obs_kind, kind.obs_dim = L.OBS_LINEAR, o
                 self.kernel_kind = kind
 
 
 from . import models  # noqa: E402,F401
+from .models import LinearModel  # noqa: E402,F401

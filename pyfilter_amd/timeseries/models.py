@@ -16,13 +16,19 @@ class                  transition                                               
 ``Verhulst``           ``v' = v + kappa (gamma - v) v dt + sigma v e``             examples/stochastic-volatility.ipynb
 ``Lorenz63``           Lorenz-63 drift, Euler-Maruyama, D = 3                      examples/lorenz.ipynb
 ``OrnsteinUhlenbeck``  exact discretisation                                        tests/inference/models.py:12-19
+``LinearModel``        ``x' = b + A x + s e``, full ``A`` (any D)                  tests/filters/models.py:28-38
 =====================  ==========================================================  =============================
+
+Shapes and routes: the kinds above with ``D, O <= 3`` run the fused one-launch kernels.  ``LinearModel`` (any D) and
+``RandomWalk(dim=D)`` with ``D`` in 4 .. 8 carry ``PF_HID_LINEAR_MAT`` (``csrc/pf_linear.hpp``; the walk as ``A = I``): with
+``D, O <= 8`` and standard-normal increments they run step by step on the stand-alone model kernels, never on the fused
+route.  Beyond 8 - or with other increments - they keep the step-by-step route with torch model arithmetic.
 """
 from math import sqrt
 from typing import Optional, Sequence, Tuple
 
 import torch
-from torch.distributions import Independent, Normal
+from torch.distributions import Distribution, Independent, Normal
 
 from .. import _lib as L
 from . import AffineProcess, KernelKind, StateSpaceModel, TimeseriesState, _as_tensor
@@ -51,7 +57,7 @@ class _BuiltinProcess(AffineProcess):
         super().__init__(
             mean_scale, parameters, _increment(inc_scale, dim), _normal_init(self.init_mean, self.init_scale, dim)
         )
-        self.kernel_kind = KernelKind(kind_id, dim, dt, inc_scale)
+        self.kernel_kind = KernelKind(kind_id, dim, dt, inc_scale) if kind_id is not None else None
         self._dim = dim
 
     def to(self, device):
@@ -86,10 +92,19 @@ class RandomWalk(_BuiltinProcess):
                 raise L.PfAmdError("RandomWalk: pass `dim` explicitly when sigma has a batch dimension")
         zeros, ones = torch.zeros_like(sigma), torch.ones_like(sigma)
         init_scale = sigma if initial_scale is None else initial_scale
+        # D = 4 .. 8: the matrix kind with A = I (the reference's own construction, LinearModel((eye(D), sigma), ...)); larger D
+        # has no kernel kind (the step-by-step route with torch model arithmetic)
+        kind = L.HID_LINEAR if dim <= L.MAX_D else (L.HID_LINEAR_MAT if dim <= L.LIN_MAX_D else None)
         super().__init__(
-            L.HID_LINEAR, lambda x, a, b, s: (a + b * x.value, s), (zeros, ones, sigma), dim, 1.0, 1.0,
+            kind, lambda x, a, b, s: (a + b * x.value, s), (zeros, ones, sigma), dim, 1.0, 1.0,
             _as_tensor(initial_mean) + zeros, init_scale,
         )
+
+    def linear_rows(self, b: int, dtype, device):
+        """``(A (B, D, D), b (B, D), s (B, D))`` of the ``PF_HID_LINEAR_MAT`` parameter row: ``A = I``, ``b = 0``."""
+        d = self._dim
+        eye = torch.eye(d, dtype=dtype, device=device).expand(b, d, d)
+        return eye, torch.zeros((b, d), dtype=dtype, device=device), _expand(self.parameters[2], b, (d,), dtype, device)
 
 
 class SineDiffusion(_BuiltinProcess):
@@ -143,6 +158,74 @@ class OrnsteinUhlenbeck(_BuiltinProcess):
         super().__init__(L.HID_OU, ms, (kappa, gamma, sigma), 0, dt, 1.0, init[0], init[1])
 
 
+class LinearModel(AffineProcess):
+    """``x' = b + A x + s e`` (stochproc's ``LinearModel``; the reference builds its acceptance model from it,
+    tests/filters/models.py:28-38: ``LinearModel((a, sigma), inc_dist, initial_kernel)``).  ``parameters`` is ``(a, s)`` or
+    ``(a, b, s)``; the initial kernel is called with ``(a, b, s)`` (or ``initial_parameters``).  A matrix ``a`` - ``(D, D)``, or
+    ``(B, D, D)`` with one matrix per filter - acts through ``matmul``, a scalar / vector ``a`` elementwise; ``b`` and ``s`` are
+    ``(D,)`` or ``(B, D)``.
+
+    With standard-normal increments (``Normal(0, 1)``, possibly ``.expand([D]).to_event(1)``) and ``D <= 8`` the process carries
+    the kernel kind ``PF_HID_LINEAR_MAT``: under a linear-Gaussian observation of ``O <= 8`` components the proposals evaluate
+    it with the stand-alone model kernels (csrc/pf_linear.hpp).  Otherwise it is an ordinary user process (torch ops)."""
+
+    def __init__(self, parameters, increment_distribution: Distribution, initial_kernel, initial_parameters=None):
+        parameters = tuple(_as_tensor(p) for p in parameters)
+        if len(parameters) == 2:
+            a, s = parameters
+            parameters = (a, torch.zeros_like(s), s)
+        if len(parameters) != 3:
+            raise ValueError("LinearModel: parameters are (a, s) or (a, b, s)")
+
+        def _ms(x, a, b, s):
+            v = x.value
+            loc = b + (a @ v.unsqueeze(-1)).squeeze(-1) if a.dim() >= 2 else b + a * v
+            return loc, s
+
+        super().__init__(_ms, parameters, increment_distribution, initial_kernel, initial_parameters)
+
+    @property
+    def kernel_kind(self) -> Optional[KernelKind]:
+        if type(self) is not LinearModel:  # (a subclass may change the dynamics the kernels would compute)
+            return None
+        d = self.event_shape.numel() if self.n_dim > 0 else 1
+        if self.n_dim > 1 or d > L.LIN_MAX_D or not _standard_normal(self.increment_distribution):
+            return None
+        a = self.parameters[0]
+        if a.dim() >= 2 and tuple(a.shape[-2:]) != (d, d):
+            return None
+        return KernelKind(L.HID_LINEAR_MAT, d, 1.0, 1.0)
+
+    def linear_rows(self, b: int, dtype, device):
+        """``(A (B, D, D), b (B, D), s (B, D))`` of the ``PF_HID_LINEAR_MAT`` parameter row."""
+        d = self.event_shape.numel() if self.n_dim > 0 else 1
+        a, off, s = self.parameters
+        a = a.to(device=device, dtype=dtype)
+        if a.dim() >= 2:
+            mat = a.expand(b, d, d) if a.dim() == 2 else _expand(a, b, (d, d), dtype, device)
+        else:
+            mat = torch.diag_embed(_expand(a, b, (d,), dtype, device))
+        return mat, _expand(off, b, (d,), dtype, device), _expand(s, b, (d,), dtype, device)
+
+
+def _standard_normal(inc) -> bool:
+    """``Normal(0, 1)`` increments (possibly reinterpreted as an event): what ``PF_HID_LINEAR_MAT`` draws.  One host copy of the
+    increment parameters per distribution object, remembered by their identity and in-place version."""
+    base = inc.base_dist if isinstance(inc, Independent) else inc
+    if not isinstance(base, Normal):
+        return False
+    key = (id(base.loc), base.loc._version, id(base.scale), base.scale._version)
+    cached = getattr(base, "_pf_std_normal", None)
+    if cached is None or cached[0] != key:
+        loc, scale = base.loc.detach().reshape(-1).cpu(), base.scale.detach().reshape(-1).cpu()
+        cached = (key, loc.numel() > 0 and not bool((loc != 0).any()) and not bool((scale != 1).any()))
+        try:
+            base._pf_std_normal = cached
+        except AttributeError:
+            pass
+    return cached[1]
+
+
 class StochasticVolatilityModel(StateSpaceModel):
     """``y ~ N(mu, scale = x)`` on a scalar volatility process - the SV notebook's observation density at
     ``skew = 0, kurt = 1`` (where its SinhArcsinh transform is the identity)."""
@@ -187,18 +270,24 @@ def _expand(p: torch.Tensor, b: int, inner: Sequence[int], dtype, device) -> tor
 
 
 def pack_params(ssm: StateSpaceModel, b: int, dtype, device) -> torch.Tensor:
-    """``(B, NP)`` rows ``[hp0[D] hp1[D] hp2[D] hp3[D] | A[OxD] | b[O] | s[O]]`` (``pf_model.params``)."""
+    """``(B, NP)`` rows ``[hp0[D] hp1[D] hp2[D] hp3[D] | A[OxD] | b[O] | s[O]]`` (``pf_model.params``); ``PF_HID_LINEAR_MAT``:
+    ``[A[DxD] | b[D] | s[D] | A[OxD] | b[O] | s[O]]``."""
     kind = ssm.kernel_kind
     if kind is None:
         raise L.PfAmdError("model has no built-in kernel kind")
     d, o = kind.dim, kind.obs_dim
     cols = []
-    hp = [] if kind.is_user else list(ssm.hidden.parameters)  # (a user process keeps its parameters in its callable)
-    for k in range(4):
-        if k < len(hp):
-            cols.append(_expand(hp[k], b, (d,), dtype, device))
-        else:
-            cols.append(torch.zeros((b, d), dtype=dtype, device=device))
+    if kind.hid_kind == L.HID_LINEAR_MAT:
+        # ``[A[D x D] | b[D] | s[D] | A_obs[O x D] | b_obs[O] | s_obs[O]]`` (include/pf_amd.h)
+        a_h, b_h, s_h = ssm.hidden.linear_rows(b, dtype, device)
+        cols += [a_h.reshape(b, d * d), b_h, s_h]
+    else:
+        hp = [] if kind.is_user else list(ssm.hidden.parameters)  # (a user process keeps its parameters in its callable)
+        for k in range(4):
+            if k < len(hp):
+                cols.append(_expand(hp[k], b, (d,), dtype, device))
+            else:
+                cols.append(torch.zeros((b, d), dtype=dtype, device=device))
     if kind.obs_kind == L.OBS_LINEAR:
         a, ob, os_ = ssm.parameters
         if d > 1 and ssm.n_dim == 0 and a.dim() >= 1:
