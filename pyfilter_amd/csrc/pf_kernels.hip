@@ -77,7 +77,7 @@ struct ColStat {
 
 // workspace carve-up (all offsets 256-byte aligned)
 struct WsLayout {
-    size_t off_part;   // double partials[2][(6 + 2D)][B][tiles]
+    size_t off_part;   // double partials[2][(6 + 2 PF_MAXD)][B][tiles]
     size_t part_elems;
     size_t off_stat;   // ColStat[B]
     size_t off_poison; // int32 [4][B]
@@ -130,11 +130,11 @@ __host__ __device__ static inline int cdf_tree_total(int64_t N) {  // entries pe
 
 static inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
-static inline WsLayout make_ws(const Geom& g, int D) {
+static inline WsLayout make_ws(const Geom& g) {  // (partials sized for PF_MAXD states)
     WsLayout w;
     size_t o = 0;
     w.off_part = o;  // two copies (the fused pipeline double-buffers them by state parity)
-    w.part_elems = (size_t)(6 + 2 * D) * g.B * g.tiles;
+    w.part_elems = (size_t)(6 + 2 * PF_MAXD) * g.B * g.tiles;
     o = align256(o + 2 * sizeof(double) * w.part_elems);
     w.off_stat = o;
     o = align256(o + sizeof(ColStat) * (size_t)g.B);
@@ -165,13 +165,13 @@ static inline WsLayout make_ws(const Geom& g, int D) {
 // Upper bound of make_ws(...).total over every tile geometry make_geom can produce for (N, B) (any `target`): the partials
 // are largest with the most tiles per column (the smallest tiles), the chunk table never holds more than
 // rounds_total + one tile's rounds per column.
-static inline size_t ws_bound(int64_t N, int64_t B, int D) {
+static inline size_t ws_bound(int64_t N, int64_t B) {
     Geom g = make_geom(N, B, (int64_t)1 << 40);  // a huge target = the smallest tiles = the most tiles per column
     const int64_t rounds_total = (N + g.round_elems - 1) / g.round_elems;
-    const size_t most_tiles = make_ws(g, D).total;
+    const size_t most_tiles = make_ws(g).total;
     g.tiles = 1;
     g.rounds_per_tile = (int)(2 * rounds_total + 2);  // tiles * rounds_per_tile <= rounds_total + rounds_per_tile <= 2 rounds_total
-    const size_t most_chunks = make_ws(g, D).total;
+    const size_t most_chunks = make_ws(g).total;
     return most_tiles + most_chunks;
 }
 
@@ -1659,8 +1659,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_ffbs(ModelDesc md, const T* __rest
 #include "pf_cluster.hpp"
 
 namespace pf {
-// pf_filter_observe -> the route that carries the run: what the theta update needs, for the length of that one call on that one
-// thread (the cluster route folds it into its launch and says so; every other route leaves it to a pf_theta_step launch)
+// pf_filter_observe -> the route that carries the run: what the theta update needs (the cluster route folds it into its launch and
+// says so; every other route leaves it to a pf_theta_step launch)
 struct ThetaFold {
     void* w;
     const void* ll;
@@ -1670,7 +1670,6 @@ struct ThetaFold {
     void* acc;
     int folded;
 };
-extern thread_local ThetaFold* tls_theta_fold;
 }  // namespace pf
 
 // =================================================================================================================
@@ -1678,11 +1677,39 @@ extern thread_local ThetaFold* tls_theta_fold;
 // =================================================================================================================
 using namespace pf;
 
-#define PF_CHECK_LAUNCH()                       \
-    do {                                        \
-        hipError_t e_ = hipGetLastError();      \
-        if (e_ != hipSuccess) return (int)e_;   \
+// PF_OK, or the error of the launches since the last check (hipGetLastError)
+static inline int launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PF_OK : (int)e;
+}
+#define PF_CHECK_LAUNCH()                          \
+    do {                                           \
+        if (const int e_ = launch_status()) return e_; \
     } while (0)
+
+// Run-time values as compile-time constants: each with_* calls the generic lambda `f` with a tag of the value and returns its result
+template <int V> using int_c = std::integral_constant<int, V>;
+// the C ABI's element type: f(float{}) or f(double{}); PF_EINVAL (nothing called) for any other dtype
+template <typename F> static inline int with_dtype(int dtype, F&& f) {
+    if (dtype == PF_F32) return f(float{});
+    if (dtype == PF_F64) return f(double{});
+    return PF_EINVAL;
+}
+// particles per lane of a tile geometry (Geom::vec): 4, else 1
+template <typename F> static inline int with_vec(int vec, F&& f) { return vec == 4 ? f(int_c<4>{}) : f(int_c<1>{}); }
+// the state dimension of the built-in models: 1, 2, else 3 (check_model bounds it)
+template <typename F> static inline int with_d3(int64_t D, F&& f) {
+    return D == 1 ? f(int_c<1>{}) : D == 2 ? f(int_c<2>{}) : f(int_c<3>{});
+}
+// ... of PF_HID_LINEAR_MAT: 1 .. 8 (PF_LIN_MAXD), PF_EUNSUPPORTED otherwise
+template <typename F> static inline int with_d8(int64_t D, F&& f) {
+    switch (D) {
+        case 1: return f(int_c<1>{}); case 2: return f(int_c<2>{}); case 3: return f(int_c<3>{}); case 4: return f(int_c<4>{});
+        case 5: return f(int_c<5>{}); case 6: return f(int_c<6>{}); case 7: return f(int_c<7>{}); case 8: return f(int_c<8>{});
+        default: return PF_EUNSUPPORTED;
+    }
+}
+template <typename F> static inline int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 static inline bool bad_shape(int64_t N, int64_t B) { return N < 1 || B < 1 || N > (int64_t)1 << 30 || B > 65535; }
 
@@ -1717,11 +1744,11 @@ static inline ModelDesc to_desc(const pf_model* m) {
 
 // The fused-run instantiation matrix compiles as several translation units (the build runs them in parallel):
 //   -DPF_TU_NO_F64 -DPF_TU_NO_F32DN -DPF_TU_NO_F32D1 : the main unit - C ABI and the stand-alone primitives
-//   -DPF_TU_F32D1_ONLY -DPF_TU_VEC=4|1 : only the float32 fused kernels of scalar states for one vector width + entry
-//   -DPF_TU_F32DN_ONLY              : only the float32 fused kernels of D > 1 states + their entry (pf_run_f32_dn)
-//   -DPF_TU_F64_ONLY                : only the float64 fused kernels + their entry               (pf_run_f64)
+//   -DPF_TU_F32D1_ONLY -DPF_TU_VEC=4|1 : only the float32 fused kernels of scalar states for one vector width
+//   -DPF_TU_F32DN_ONLY              : only the float32 fused kernels of D > 1 states
+//   -DPF_TU_F64_ONLY                : only the float64 fused kernels
 //   ... each of the kernel units additionally with -DPF_TU_MULTI=0|1: only the kernels of single-round / multi-round
-//   tiles (the MULTI template argument of k_fused_step; entries carry the suffix _m0 / _m1)
+//   tiles (the MULTI template argument of k_fused_step) - with their entries, the filter_run_impl instantiations (see below)
 // Without any of the macros the file is a single self-contained unit.
 #if defined(PF_TU_COLUMN_F32) || defined(PF_TU_COLUMN_F64) || defined(PF_TU_CLUSTER_F32) || defined(PF_TU_CLUSTER_F64)
 // the column-persistent / column-cluster kernels of one arithmetic type, nothing else
@@ -1733,6 +1760,9 @@ static inline ModelDesc to_desc(const pf_model* m) {
 #if defined(PF_TU_NO_F64) || defined(PF_TU_NO_F32DN) || defined(PF_TU_NO_F32D1) || defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
 #define PF_TU_SPLIT  // a split build: the column kernels live in their own units (PF_TU_COLUMN_F32 / _F64)
 #endif
+#if !defined(PF_TU_SPLIT) || defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
+#define PF_TU_STEP  // the unit compiles k_fused_step kernels: filter_run_impl's definition and the instantiations it owns
+#endif
 #if defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
 #define PF_TU_NO_API
 #endif
@@ -1742,7 +1772,6 @@ static inline ModelDesc to_desc(const pf_model* m) {
 #endif
 #define PF_STR2(x) #x
 #define PF_STR(x) PF_STR2(x)
-namespace pf { thread_local ThetaFold* tls_theta_fold = nullptr; }
 extern "C" const char* pf_version(void) { return "pfamd 0.2.0 (gfx950) abi " PF_STR(PF_ABI_VERSION) " src:" PF_SOURCE_SHA256; }
 extern "C" int pf_abi_version(void) { return PF_ABI_VERSION; }
 
@@ -1761,7 +1790,7 @@ extern "C" const char* pf_error_string(int code) {
 #ifdef PF_DEVTOOLS  // (the instrumented build only - tools/pmc_stages.py --build: where the workspace keeps the development timestamps)
 extern "C" int pf_debug_offset(int64_t N, int64_t B, size_t* off) {
     if (!off || bad_shape(N, B)) return PF_EINVAL;
-    *off = make_ws(make_geom(N, B), PF_MAXD).off_dbg;
+    *off = make_ws(make_geom(N, B)).off_dbg;
     return PF_OK;
 }
 #endif
@@ -1769,40 +1798,40 @@ extern "C" int pf_debug_offset(int64_t N, int64_t B, size_t* off) {
 // (any D: pf_moments reduces the planes in groups of PF_MAXD, so the stand-alone primitives need no more than a PF_MAXD problem)
 extern "C" int pf_workspace_bytes(int64_t N, int64_t B, int64_t D, size_t* bytes) {
     if (!bytes || bad_shape(N, B) || D < 1) return PF_EINVAL;
-    *bytes = ws_bound(N, B, PF_MAXD);
+    *bytes = ws_bound(N, B);
     return PF_OK;
 }
 
-#define PF_DISPATCH_T_VEC(dtype, vec, CALL)                       \
-    if (dtype == PF_F32) {                                        \
-        if (vec == 4) { CALL(float, 4) } else { CALL(float, 1) }  \
-    } else if (dtype == PF_F64) {                                 \
-        if (vec == 4) { CALL(double, 4) } else { CALL(double, 1) }\
-    } else return PF_EINVAL;
+// the tile-geometry primitives' launch context: geometry, workspace layout (its size the caller checks), partials, stream, grid
+struct TileLaunch {
+    Geom g;
+    WsLayout wl;
+    double* part;
+    hipStream_t st;
+    dim3 grid;
+    TileLaunch(int64_t N, int64_t B, void* ws, void* stream)
+        : g(make_geom(N, B)), wl(make_ws(g)), part((double*)((char*)ws + wl.off_part)), st((hipStream_t)stream), grid(g.tiles, g.B) {}
+};
 
 extern "C" int pf_normalize(void* logw, void* W, void* lse, void* ess, int64_t N, int64_t B, int dtype, void* ws,
                             size_t ws_bytes, void* stream) {
     if (!logw || !ws || bad_shape(N, B)) return PF_EINVAL;
-    const Geom g = make_geom(N, B);
-    const WsLayout wl = make_ws(g, PF_MAXD);
-    if (ws_bytes < wl.total) return PF_EWORKSPACE;
-    double* part = (double*)((char*)ws + wl.off_part);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(g.tiles, g.B);
-#define CALL(T, V)                                                                                                   \
-    if (g.tiles == 1) { /* one tile per column: both passes in one launch */                                          \
-        hipLaunchKernelGGL((k_normalize_one_tile<T, V>), grid, dim3(PF_BLOCK), 0, st, (T*)logw, (T*)W, (T*)lse,      \
-                           (T*)ess, part, g);                                                                        \
-    } else {                                                                                                         \
-        hipLaunchKernelGGL((k_reduce_logw<T, V>), grid, dim3(PF_BLOCK), 0, st, (T*)logw, 1, (const uint8_t*)nullptr, \
-                           part, g);                                                                                 \
-        hipLaunchKernelGGL((k_normalize_write<T, V>), grid, dim3(PF_BLOCK), 0, st, (const T*)logw, (T*)W, (T*)lse,   \
-                           (T*)ess, (const double*)part, g);                                                         \
-    }
-    PF_DISPATCH_T_VEC(dtype, g.vec, CALL)
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    const TileLaunch p(N, B, ws, stream);
+    if (ws_bytes < p.wl.total) return PF_EWORKSPACE;
+    return with_dtype(dtype, [&](auto t) {
+        return with_vec(p.g.vec, [&](auto v) {
+            using T = decltype(t);
+            constexpr int V = decltype(v)::value;
+            if (p.g.tiles == 1) {  // one tile per column: both passes in one launch
+                hipLaunchKernelGGL((k_normalize_one_tile<T, V>), p.grid, dim3(PF_BLOCK), 0, p.st, (T*)logw, (T*)W, (T*)lse, (T*)ess, p.part, p.g);
+            } else {
+                hipLaunchKernelGGL((k_reduce_logw<T, V>), p.grid, dim3(PF_BLOCK), 0, p.st, (T*)logw, 1, (const uint8_t*)nullptr, p.part, p.g);
+                hipLaunchKernelGGL((k_normalize_write<T, V>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)logw, (T*)W, (T*)lse, (T*)ess,
+                                   (const double*)p.part, p.g);
+            }
+            return launch_status();
+        });
+    });
 }
 
 // pf_systematic without a cdf (k_chunk_scan + k_chunk_search): columns of several tiles of whole 4-vectors, one u per column, a
@@ -1822,65 +1851,60 @@ static int systematic_impl(void* src, bool from_w, const void* u, int u_per_elem
                            uint32_t step, const uint8_t* colmask, void* cdf, int32_t* idx, int64_t N, int64_t B,
                            int dtype, void* ws, size_t ws_bytes, void* stream) {
     if (!src || !idx || !ws || bad_shape(N, B) || (!multinomial && !u)) return PF_EINVAL;
-    const Geom g = make_geom(N, B);
-    const WsLayout wl = make_ws(g, PF_MAXD);
-    if (ws_bytes < wl.total) return PF_EWORKSPACE;
-    double* part = (double*)((char*)ws + wl.off_part);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(g.tiles, g.B);
+    const TileLaunch p(N, B, ws, stream);
+    const Geom& g = p.g;
+    if (ws_bytes < p.wl.total) return PF_EWORKSPACE;
     if (!cdf) {  // no cdf wanted: the two-launch form where it applies (pf_systematic_cdf_free), nothing else
         if (multinomial || !cdf_free_applies(g, dtype, u_per_elem)) return PF_EINVAL;
-        double* cb = (double*)((char*)ws + wl.off_ctab);
+        double* cb = (double*)((char*)ws + p.wl.off_ctab);
         const int nchunks = (int)((N + PF_CHUNK - 1) / PF_CHUNK);
 #ifdef PF_DEVTOOLS  // (the instrumented build: cycle stamps of the middle workgroup of column 0, tools/chunk_search_stages.py)
-#define PF_CHUNK_DBG , (unsigned long long*)((char*)ws + wl.off_dbg)
+#define PF_CHUNK_DBG , (unsigned long long*)((char*)ws + p.wl.off_dbg)
 #else
 #define PF_CHUNK_DBG
 #endif
-#define PF_CHUNK_CALL(T, FW)                                                                                                 \
-    hipLaunchKernelGGL((k_chunk_scan<T, FW>), grid, dim3(PF_BLOCK), 0, st, (T*)src, colmask, part, cb, g, nchunks);           \
-    hipLaunchKernelGGL((k_chunk_search<T, FW>), grid, dim3(PF_BLOCK), 0, st, (const T*)src, (const T*)u, colmask,             \
-                       (const double*)part, (const double*)cb, idx, g, nchunks PF_CHUNK_DBG);
-        if (dtype == PF_F32) {
-            if (from_w) { PF_CHUNK_CALL(float, true) } else { PF_CHUNK_CALL(float, false) }
-        } else {
-            if (from_w) { PF_CHUNK_CALL(double, true) } else { PF_CHUNK_CALL(double, false) }
-        }
-#undef PF_CHUNK_CALL
+        return with_dtype(dtype, [&](auto t) {
+            return with_bool(from_w, [&](auto fw) {
+                using T = decltype(t);
+                constexpr bool FW = decltype(fw)::value;
+                hipLaunchKernelGGL((k_chunk_scan<T, FW>), p.grid, dim3(PF_BLOCK), 0, p.st, (T*)src, colmask, p.part, cb, g, nchunks);
+                hipLaunchKernelGGL((k_chunk_search<T, FW>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)src, (const T*)u, colmask,
+                                   (const double*)p.part, (const double*)cb, idx, g, nchunks PF_CHUNK_DBG);
+                return launch_status();
+            });
+        });
 #undef PF_CHUNK_DBG
-        PF_CHECK_LAUNCH();
-        return PF_OK;
     }
-    void* tree = multinomial ? (void*)((char*)ws + wl.off_tree) : nullptr;  // (the iid draws' 16-ary search tables, written by the scan)
-#define CALL_MN(T, V, MN)                                                                                            \
-    if (g.tiles == 1) { /* one tile per column: record -> scan -> ancestors in one launch */                          \
-        if (from_w)                                                                                                  \
-            hipLaunchKernelGGL((k_resample_one_tile<T, V, true, MN>), grid, dim3(PF_BLOCK), 0, st, (T*)src,          \
-                               (const T*)u, u_per_elem, (const T*)v, seed, step, colmask, (T*)cdf, idx, part, g,     \
-                               (T*)tree);                                                                            \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_resample_one_tile<T, V, false, MN>), grid, dim3(PF_BLOCK), 0, st, (T*)src,         \
-                               (const T*)u, u_per_elem, (const T*)v, seed, step, colmask, (T*)cdf, idx, part, g,     \
-                               (T*)tree);                                                                            \
-    } else {                                                                                                         \
-        if (from_w) {                                                                                                \
-            hipLaunchKernelGGL((k_tile_sum<T, V>), grid, dim3(PF_BLOCK), 0, st, (const T*)src, colmask, part, g);    \
-            hipLaunchKernelGGL((k_scan<T, V, true>), grid, dim3(PF_BLOCK), 0, st, (const T*)src, (T*)cdf, colmask,   \
-                               (const double*)part, g, (T*)tree);                                                    \
-        } else {                                                                                                     \
-            hipLaunchKernelGGL((k_reduce_logw<T, V>), grid, dim3(PF_BLOCK), 0, st, (T*)src, 1, colmask, part, g);    \
-            hipLaunchKernelGGL((k_scan<T, V, false>), grid, dim3(PF_BLOCK), 0, st, (const T*)src, (T*)cdf, colmask,  \
-                               (const double*)part, g, (T*)tree);                                                    \
-        }                                                                                                            \
-        hipLaunchKernelGGL((k_search<T, V, MN>), grid, dim3(PF_BLOCK), 0, st, (const T*)cdf, (const T*)u,            \
-                           u_per_elem, (const T*)v, seed, step, colmask, idx, g, /*force_search*/ 0, (const T*)tree);\
-    }
-#define CALL(T, V) if (multinomial) { CALL_MN(T, V, true) } else { CALL_MN(T, V, false) }
-    PF_DISPATCH_T_VEC(dtype, g.vec, CALL)
-#undef CALL
-#undef CALL_MN
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    void* tree = multinomial ? (void*)((char*)ws + p.wl.off_tree) : nullptr;  // (the iid draws' 16-ary search tables, written by the scan)
+    return with_dtype(dtype, [&](auto t) {
+        return with_vec(g.vec, [&](auto vec_c) {
+            return with_bool(multinomial, [&](auto mn) {
+                using T = decltype(t);
+                constexpr int V = decltype(vec_c)::value;
+                constexpr bool MN = decltype(mn)::value;
+                if (g.tiles == 1) {  // one tile per column: record -> scan -> ancestors in one launch
+                    with_bool(from_w, [&](auto fw) {
+                        hipLaunchKernelGGL((k_resample_one_tile<T, V, decltype(fw)::value, MN>), p.grid, dim3(PF_BLOCK), 0, p.st, (T*)src,
+                                           (const T*)u, u_per_elem, (const T*)v, seed, step, colmask, (T*)cdf, idx, p.part, g, (T*)tree);
+                        return PF_OK;
+                    });
+                } else {
+                    if (from_w) {
+                        hipLaunchKernelGGL((k_tile_sum<T, V>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)src, colmask, p.part, g);
+                        hipLaunchKernelGGL((k_scan<T, V, true>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)src, (T*)cdf, colmask,
+                                           (const double*)p.part, g, (T*)tree);
+                    } else {
+                        hipLaunchKernelGGL((k_reduce_logw<T, V>), p.grid, dim3(PF_BLOCK), 0, p.st, (T*)src, 1, colmask, p.part, g);
+                        hipLaunchKernelGGL((k_scan<T, V, false>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)src, (T*)cdf, colmask,
+                                           (const double*)p.part, g, (T*)tree);
+                    }
+                    hipLaunchKernelGGL((k_search<T, V, MN>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)cdf, (const T*)u, u_per_elem,
+                                       (const T*)v, seed, step, colmask, idx, g, /*force_search*/ 0, (const T*)tree);
+                }
+                return launch_status();
+            });
+        });
+    });
 }
 
 extern "C" int pf_systematic(const void* W, const void* u, int u_per_element, const uint8_t* colmask, void* cdf,
@@ -1913,13 +1937,11 @@ extern "C" int pf_gather(const void* x, const int32_t* idx, const uint8_t* colma
     if (!x || !idx || !out || bad_shape(N, B) || D < 1 || x == out) return PF_EINVAL;
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_gather<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)x, idx, colmask, (float*)out, N, (int)B, (int)D);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_gather<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)x, idx, colmask, (double*)out, N, (int)B, (int)D);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_gather<T>), grid, dim3(PF_BLOCK), 0, st, (const T*)x, idx, colmask, (T*)out, N, (int)B, (int)D);
+        return launch_status();
+    });
 }
 
 static int columns_move(const void* src, const int64_t* idx, const uint8_t* mask, void* dst, int64_t N, int64_t B,
@@ -1953,70 +1975,37 @@ extern "C" int pf_columns_exchange(void* dst, const void* src, const uint8_t* ma
 extern "C" int pf_loglik(const void* v, const void* W, void* out, int64_t N, int64_t B, int dtype, void* ws,
                          size_t ws_bytes, void* stream) {
     if (!v || !out || !ws || bad_shape(N, B)) return PF_EINVAL;
-    const Geom g = make_geom(N, B);
-    const WsLayout wl = make_ws(g, PF_MAXD);
-    if (ws_bytes < wl.total) return PF_EWORKSPACE;
-    double* part = (double*)((char*)ws + wl.off_part);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(g.tiles, g.B);
-    if (dtype == PF_F32) {
-        hipLaunchKernelGGL((k_loglik_part<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)v, (const float*)W, part, g);
-        hipLaunchKernelGGL((k_loglik_final<float>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (float*)out, g);
-    } else if (dtype == PF_F64) {
-        hipLaunchKernelGGL((k_loglik_part<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)v, (const double*)W, part, g);
-        hipLaunchKernelGGL((k_loglik_final<double>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (double*)out, g);
-    } else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    const TileLaunch p(N, B, ws, stream);
+    if (ws_bytes < p.wl.total) return PF_EWORKSPACE;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_loglik_part<T>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)v, (const T*)W, p.part, p.g);
+        hipLaunchKernelGGL((k_loglik_final<T>), dim3(p.g.B), dim3(PF_BLOCK), 0, p.st, (const double*)p.part, (T*)out, p.g);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_moments(const void* x, const void* W, void* mean, void* var, int64_t N, int64_t B, int64_t D,
                           int dtype, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !W || !mean || !var || !ws || bad_shape(N, B) || D < 1) return PF_EINVAL;
-    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
-    const Geom g = make_geom(N, B);
-    const WsLayout wl = make_ws(g, PF_MAXD);
-    if (ws_bytes < wl.total) return PF_EWORKSPACE;
-    double* part = (double*)((char*)ws + wl.off_part);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(g.tiles, g.B);
-    // the planes in groups of PF_MAXD (one pair of launches per group, the same partial slots reused in stream order)
-    const int64_t plane = N * B;
-    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
-        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
-        if (dtype == PF_F32) {
-            hipLaunchKernelGGL((k_moments_part<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)x + d0 * plane, (const float*)W, part, g, dg);
-            hipLaunchKernelGGL((k_moments_final<float>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (float*)mean, (float*)var, g,
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const TileLaunch p(N, B, ws, stream);
+        if (ws_bytes < p.wl.total) return PF_EWORKSPACE;
+        // the planes in groups of PF_MAXD (one pair of launches per group, the same partial slots reused in stream order)
+        const int64_t plane = N * B;
+        for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+            const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+            hipLaunchKernelGGL((k_moments_part<T>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)x + d0 * plane, (const T*)W, p.part, p.g, dg);
+            hipLaunchKernelGGL((k_moments_final<T>), dim3(p.g.B), dim3(PF_BLOCK), 0, p.st, (const double*)p.part, (T*)mean, (T*)var, p.g,
                                dg, (int)d0, (int)D);
-        } else {
-            hipLaunchKernelGGL((k_moments_part<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)x + d0 * plane, (const double*)W, part, g, dg);
-            hipLaunchKernelGGL((k_moments_final<double>), dim3(g.B), dim3(PF_BLOCK), 0, st, (const double*)part, (double*)mean, (double*)var, g,
-                               dg, (int)d0, (int)D);
+            PF_CHECK_LAUNCH();
         }
-        PF_CHECK_LAUNCH();
-    }
-    return PF_OK;
+        return PF_OK;
+    });
 }
 
 
-
-#define PF_DISPATCH_T_D(dtype, D, CALL)                                                     \
-    if (dtype == PF_F32) {                                                                  \
-        if (D == 1) { CALL(float, 1) } else if (D == 2) { CALL(float, 2) } else { CALL(float, 3) }      \
-    } else if (dtype == PF_F64) {                                                           \
-        if (D == 1) { CALL(double, 1) } else if (D == 2) { CALL(double, 2) } else { CALL(double, 3) }   \
-    } else return PF_EINVAL;
-
-// PF_HID_LINEAR_MAT: the state dimension as a template argument, 1 .. 8 (check_model bounds it)
-#define PF_DISPATCH_D8(T, D, CALL)                                                                                  \
-    switch (D) {                                                                                                    \
-        case 1: { CALL(T, 1) } break; case 2: { CALL(T, 2) } break; case 3: { CALL(T, 3) } break;                    \
-        case 4: { CALL(T, 4) } break; case 5: { CALL(T, 5) } break; case 6: { CALL(T, 6) } break;                    \
-        case 7: { CALL(T, 7) } break; case 8: { CALL(T, 8) } break; default: return PF_EUNSUPPORTED;                  \
-    }
-#define PF_DISPATCH_T_D8(dtype, D, CALL)                                                                            \
-    if (dtype == PF_F32) { PF_DISPATCH_D8(float, D, CALL) } else if (dtype == PF_F64) { PF_DISPATCH_D8(double, D, CALL) } \
-    else return PF_EINVAL;
 
 extern "C" int pf_pre_weight(const pf_model* model, int proposal, const void* x, const void* y, int64_t y_rows,
                              void* out, int64_t N, int64_t B, int dtype, void* stream) {
@@ -2027,22 +2016,20 @@ extern "C" int pf_pre_weight(const pf_model* model, int proposal, const void* x,
     const ModelDesc md = to_desc(model);
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (model->hid_kind == PF_HID_LINEAR_MAT) {
-#define CALL(T, DD)                                                                                                                  \
-    hipLaunchKernelGGL((k_linmat_pre_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params, (int)model->obs_dim, proposal, \
-                       (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
-        PF_DISPATCH_T_D8(dtype, model->dim, CALL)
-#undef CALL
-        PF_CHECK_LAUNCH();
-        return PF_OK;
-    }
-#define CALL(T, DD)                                                                                                  \
-    hipLaunchKernelGGL((k_pre_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, proposal,    \
-                       (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
-    PF_DISPATCH_T_D(dtype, model->dim, CALL)
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (model->hid_kind == PF_HID_LINEAR_MAT)
+            return with_d8(model->dim, [&](auto d) {
+                hipLaunchKernelGGL((k_linmat_pre_weight<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params,
+                                   (int)model->obs_dim, proposal, (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
+                return launch_status();
+            });
+        return with_d3(model->dim, [&](auto d) {
+            hipLaunchKernelGGL((k_pre_weight<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, proposal,
+                               (const T*)x, (const T*)y, (int)y_rows, (T*)out, N, (int)B);
+            return launch_status();
+        });
+    });
 }
 
 extern "C" int pf_sample_and_weight(const pf_model* model, int proposal, int weigh, const void* x, const void* y,
@@ -2055,47 +2042,44 @@ extern "C" int pf_sample_and_weight(const pf_model* model, int proposal, int wei
     const ModelDesc md = to_desc(model);
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (model->hid_kind == PF_HID_LINEAR_MAT) {
-#define CALL(T, DD)                                                                                                                  \
-    hipLaunchKernelGGL((k_linmat_sample_and_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params, (int)model->obs_dim,      \
-                       proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step, (T*)x_out, (T*)w_out, N, (int)B);
-        PF_DISPATCH_T_D8(dtype, model->dim, CALL)
-#undef CALL
-        PF_CHECK_LAUNCH();
-        return PF_OK;
-    }
-#define CALL(T, DD)                                                                                                  \
-    hipLaunchKernelGGL((k_sample_and_weight<T, DD>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params,       \
-                       proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step, (T*)x_out,   \
-                       (T*)w_out, N, (int)B);
-    PF_DISPATCH_T_D(dtype, model->dim, CALL)
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (model->hid_kind == PF_HID_LINEAR_MAT)
+            return with_d8(model->dim, [&](auto d) {
+                hipLaunchKernelGGL((k_linmat_sample_and_weight<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params,
+                                   (int)model->obs_dim, proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step,
+                                   (T*)x_out, (T*)w_out, N, (int)B);
+                return launch_status();
+            });
+        return with_d3(model->dim, [&](auto d) {
+            hipLaunchKernelGGL((k_sample_and_weight<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
+                               proposal, weigh, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, seed, step, (T*)x_out, (T*)w_out, N,
+                               (int)B);
+            return launch_status();
+        });
+    });
 }
 
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;
-    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
     // planes in groups of PF_MAXD; group k draws its Philox normals at step k (group 0: the draws of a D <= 3 state)
     const int64_t plane = N * B;
-    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
-        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
-        double m[3] = {0, 0, 0}, s[3] = {0, 0, 0};
-        for (int d = 0; d < dg; ++d) { m[d] = m0[d0 + d]; s[d] = s0[d0 + d]; }
-        const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
-        if (dtype == PF_F32)
-            hipLaunchKernelGGL((k_initial_sample<float>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2],
-                               z ? (const float*)z + d0 * plane : nullptr, seed, (float*)x + d0 * plane, N, (int)B, dg, grp);
-        else
-            hipLaunchKernelGGL((k_initial_sample<double>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2],
-                               z ? (const double*)z + d0 * plane : nullptr, seed, (double*)x + d0 * plane, N, (int)B, dg, grp);
-        PF_CHECK_LAUNCH();
-    }
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+            const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+            double m[3] = {0, 0, 0}, s[3] = {0, 0, 0};
+            for (int d = 0; d < dg; ++d) { m[d] = m0[d0 + d]; s[d] = s0[d0 + d]; }
+            const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
+            hipLaunchKernelGGL((k_initial_sample<T>), grid, dim3(PF_BLOCK), 0, st, m[0], m[1], m[2], s[0], s[1], s[2],
+                               z ? (const T*)z + d0 * plane : nullptr, seed, (T*)x + d0 * plane, N, (int)B, dg, grp);
+            PF_CHECK_LAUNCH();
+        }
+        return PF_OK;
+    });
 }
 
 
@@ -2105,36 +2089,33 @@ extern "C" int pf_initial_sample_cols(const void* m0, int64_t m0_stride_b, int64
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1 || m0_stride_b < 0 || m0_stride_d < 0 || s0_stride_b < 0 ||
         s0_stride_d < 0)
         return PF_EINVAL;
-    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
     // (the plane groups of pf_initial_sample, the same draws)
     const int64_t plane = N * B;
-    for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
-        const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
-        const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
-        if (dtype == PF_F32)
-            hipLaunchKernelGGL((k_initial_sample_cols<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)m0 + d0 * m0_stride_d, m0_stride_b,
-                               m0_stride_d, (const float*)s0 + d0 * s0_stride_d, s0_stride_b, s0_stride_d,
-                               z ? (const float*)z + d0 * plane : nullptr, seed, (float*)x + d0 * plane, N, (int)B, dg, grp);
-        else
-            hipLaunchKernelGGL((k_initial_sample_cols<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)m0 + d0 * m0_stride_d, m0_stride_b,
-                               m0_stride_d, (const double*)s0 + d0 * s0_stride_d, s0_stride_b, s0_stride_d,
-                               z ? (const double*)z + d0 * plane : nullptr, seed, (double*)x + d0 * plane, N, (int)B, dg, grp);
-        PF_CHECK_LAUNCH();
-    }
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
+            const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
+            const uint32_t grp = (uint32_t)(d0 / PF_MAXD);
+            hipLaunchKernelGGL((k_initial_sample_cols<T>), grid, dim3(PF_BLOCK), 0, st, (const T*)m0 + d0 * m0_stride_d, m0_stride_b,
+                               m0_stride_d, (const T*)s0 + d0 * s0_stride_d, s0_stride_b, s0_stride_d,
+                               z ? (const T*)z + d0 * plane : nullptr, seed, (T*)x + d0 * plane, N, (int)B, dg, grp);
+            PF_CHECK_LAUNCH();
+        }
+        return PF_OK;
+    });
 }
 
 extern "C" int pf_observed_flags(const void* y, int64_t steps, int64_t row_elems, int dtype, uint8_t* out, void* stream) {
     if (!y || !out || steps < 0 || row_elems < 1 || steps > 0x7fffffff) return PF_EINVAL;
     if (steps == 0) return PF_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32) hipLaunchKernelGGL((k_observed_flags<float>), dim3((unsigned)steps), dim3(PF_WAVE), 0, st, (const float*)y, row_elems, out);
-    else if (dtype == PF_F64) hipLaunchKernelGGL((k_observed_flags<double>), dim3((unsigned)steps), dim3(PF_WAVE), 0, st, (const double*)y, row_elems, out);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_observed_flags<T>), dim3((unsigned)steps), dim3(PF_WAVE), 0, st, (const T*)y, row_elems, out);
+        return launch_status();
+    });
 }
 
 // ---- theta-level kernels (pf_theta.hpp) ---------------------------------------------------------------------------------
@@ -2143,15 +2124,12 @@ extern "C" int pf_theta_fit(const void* values, const void* logw, int64_t B, int
                             void* chol, void* stream) {
     if (!values || !mean || !chol || B < 1 || P < 1 || P > PF_THETA_MAXP) return PF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_theta_fit<float>), dim3(1), dim3(PF_BLOCK), 0, st, (const float*)values, (const float*)logw, B, (int)P, scale,
-                           (float*)mean, (float*)chol);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_theta_fit<double>), dim3(1), dim3(PF_BLOCK), 0, st, (const double*)values, (const double*)logw, B, (int)P,
-                           scale, (double*)mean, (double*)chol);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_fit<T>), dim3(1), dim3(PF_BLOCK), 0, st, (const T*)values, (const T*)logw, B, (int)P, scale, (T*)mean,
+                           (T*)chol);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_theta_propose(const pf_theta_priors* priors, const void* mean, const void* chol, const void* eps, int64_t B,
@@ -2170,15 +2148,12 @@ extern "C" int pf_theta_propose(const pf_theta_priors* priors, const void* mean,
     }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((B + PF_BLOCK - 1) / PF_BLOCK));
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_theta_propose<float>), grid, dim3(PF_BLOCK), 0, st, pr, (const float*)mean, (const float*)chol,
-                           (const float*)eps, B, (float*)u_out, out, (float*)prior_out);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_theta_propose<double>), grid, dim3(PF_BLOCK), 0, st, pr, (const double*)mean, (const double*)chol,
-                           (const double*)eps, B, (double*)u_out, out, (double*)prior_out);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_propose<T>), grid, dim3(PF_BLOCK), 0, st, pr, (const T*)mean, (const T*)chol, (const T*)eps, B,
+                           (T*)u_out, out, (T*)prior_out);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_theta_accept(const void* u_cur, const void* u_star, const void* mean_f, const void* chol_f, const void* mean_r,
@@ -2189,14 +2164,13 @@ extern "C" int pf_theta_accept(const void* u_cur, const void* u_star, const void
         !log_acc || !accepted || !rate || B < 1 || P < 1 || P > PF_THETA_MAXP)
         return PF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-#define CALL(T)                                                                                                               \
-    hipLaunchKernelGGL((k_theta_accept<T>), dim3(1), dim3(PF_BLOCK), 0, st, (const T*)u_cur, (const T*)u_star, (const T*)mean_f, \
-                       (const T*)chol_f, (const T*)mean_r, (const T*)chol_r, (const T*)prior_cur, (const T*)prior_star,         \
-                       (const T*)ll_cur, (const T*)ll_star, (const T*)unif, B, (int)P, (T*)log_acc, accepted, (T*)rate);
-    if (dtype == PF_F32) { CALL(float) } else if (dtype == PF_F64) { CALL(double) } else return PF_EINVAL;
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_accept<T>), dim3(1), dim3(PF_BLOCK), 0, st, (const T*)u_cur, (const T*)u_star, (const T*)mean_f,
+                           (const T*)chol_f, (const T*)mean_r, (const T*)chol_r, (const T*)prior_cur, (const T*)prior_star,
+                           (const T*)ll_cur, (const T*)ll_star, (const T*)unif, B, (int)P, (T*)log_acc, accepted, (T*)rate);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_theta_path(const void* w0, const void* ll, int64_t n, int64_t B, int dtype, void* w_path, void* stats,
@@ -2204,30 +2178,24 @@ extern "C" int pf_theta_path(const void* w0, const void* ll, int64_t n, int64_t 
     if (!w0 || !ll || !w_path || !stats || B < 1 || n < 0 || n > 65535 || ((uintptr_t)host_rows & 7) != 0) return PF_EINVAL;
     if (n == 0) return PF_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_theta_path<float>), dim3((unsigned)n), dim3(PF_BLOCK), 0, st, (const float*)w0, (const float*)ll, B,
-                           (float*)w_path, (float*)stats, (double*)host_rows, (unsigned long long)seq, (float*)nullptr, (const int*)status, 1);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_theta_path<double>), dim3((unsigned)n), dim3(PF_BLOCK), 0, st, (const double*)w0, (const double*)ll, B,
-                           (double*)w_path, (double*)stats, (double*)host_rows, (unsigned long long)seq, (double*)nullptr, (const int*)status, 1);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_path<T>), dim3((unsigned)n), dim3(PF_BLOCK), 0, st, (const T*)w0, (const T*)ll, B, (T*)w_path,
+                           (T*)stats, (double*)host_rows, (unsigned long long)seq, (T*)nullptr, (const int*)status, 1);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_theta_step(void* w, const void* ll, int64_t B, int dtype, void* stats, void* host_slot, uint64_t seq, void* acc,
                              const int32_t* status, void* stream) {
     if (!w || !ll || !stats || B < 1 || ((uintptr_t)host_slot & 7) != 0) return PF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_theta_path<float>), dim3(1), dim3(PF_BLOCK), 0, st, (const float*)w, (const float*)ll, B, (float*)w,
-                           (float*)stats, (double*)host_slot, (unsigned long long)seq, (float*)acc, (const int*)status);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_theta_path<double>), dim3(1), dim3(PF_BLOCK), 0, st, (const double*)w, (const double*)ll, B, (double*)w,
-                           (double*)stats, (double*)host_slot, (unsigned long long)seq, (double*)acc, (const int*)status);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_path<T>), dim3(1), dim3(PF_BLOCK), 0, st, (const T*)w, (const T*)ll, B, (T*)w, (T*)stats,
+                           (double*)host_slot, (unsigned long long)seq, (T*)acc, (const int*)status);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_host_alloc(size_t bytes, void** out) {
@@ -2255,13 +2223,11 @@ extern "C" int pf_theta_resample(const void* logw, int64_t B, double u, int dtyp
                                  void* stream) {
     if (!logw || !ancestors || !cdf_scratch || B < 1 || !(u >= 0.0 && u <= 1.0)) return PF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_theta_resample<float>), dim3(1), dim3(PF_BLOCK), 0, st, (const float*)logw, B, u, ancestors, (float*)cdf_scratch);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_theta_resample<double>), dim3(1), dim3(PF_BLOCK), 0, st, (const double*)logw, B, u, ancestors, (double*)cdf_scratch);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_resample<T>), dim3(1), dim3(PF_BLOCK), 0, st, (const T*)logw, B, u, ancestors, (T*)cdf_scratch);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_theta_ess(const void* logw, int64_t rows, int64_t B, int dtype, void* out, void* stream) {
@@ -2269,11 +2235,11 @@ extern "C" int pf_theta_ess(const void* logw, int64_t rows, int64_t B, int dtype
     if (rows == 0) return PF_OK;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)rows);
-    if (dtype == PF_F32) hipLaunchKernelGGL((k_theta_ess<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)logw, B, (float*)out);
-    else if (dtype == PF_F64) hipLaunchKernelGGL((k_theta_ess<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)logw, B, (double*)out);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_theta_ess<T>), grid, dim3(PF_BLOCK), 0, st, (const T*)logw, B, (T*)out);
+        return launch_status();
+    });
 }
 
 
@@ -2284,13 +2250,11 @@ extern "C" int pf_smooth_fixed_lag(const void* x_hist, const int32_t* anc_hist, 
     if (!x_hist || !anc_hist || !out || S < 1 || bad_shape(N, B) || D < 1) return PF_EINVAL;  // (any D: the planes are looped)
     const dim3 grid(ew_blocks(N), (int)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PF_F32)
-        hipLaunchKernelGGL((k_trace_ancestors<float>), grid, dim3(PF_BLOCK), 0, st, (const float*)x_hist, anc_hist, (float*)out, S, N, (int)B, (int)D);
-    else if (dtype == PF_F64)
-        hipLaunchKernelGGL((k_trace_ancestors<double>), grid, dim3(PF_BLOCK), 0, st, (const double*)x_hist, anc_hist, (double*)out, S, N, (int)B, (int)D);
-    else return PF_EINVAL;
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_trace_ancestors<T>), grid, dim3(PF_BLOCK), 0, st, (const T*)x_hist, anc_hist, (T*)out, S, N, (int)B, (int)D);
+        return launch_status();
+    });
 }
 
 extern "C" int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const void* logw_hist, const void* x_last,
@@ -2303,13 +2267,14 @@ extern "C" int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const v
     const ModelDesc md = to_desc(model);
     const dim3 grid((unsigned)((N + PF_BLOCK - 1) / PF_BLOCK), (int)B);
     hipStream_t st = (hipStream_t)stream;
-#define CALL(T, DD)                                                                                                         \
-    hipLaunchKernelGGL((k_ffbs<T, DD>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, (const T*)x_hist,          \
-                       (const T*)logw_hist, (const T*)x_last, (const T*)u, seed, (T*)out, S, N, (int)B);
-    PF_DISPATCH_T_D(dtype, model->dim, CALL)
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        return with_d3(model->dim, [&](auto d) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_ffbs<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, (const T*)x_hist,
+                               (const T*)logw_hist, (const T*)x_last, (const T*)u, seed, (T*)out, S, N, (int)B);
+            return launch_status();
+        });
+    });
 }
 
 // ---- test support ----------------------------------------------------------------------------------------------------
@@ -2319,15 +2284,16 @@ extern "C" int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_st
     const Geom g = make_geom(N, B);
     const dim3 grid((unsigned)((N + g.round_elems - 1) / g.round_elems), (unsigned)B, (unsigned)n_steps);
     hipStream_t st = (hipStream_t)stream;
-#define CALL(T, DD, V) hipLaunchKernelGGL((k_debug_normals<T, DD, V>), grid, dim3(PF_BLOCK), 0, st, seed, step0, (T*)out, N, (int)B)
-#define CALL_D(T, V) do { if (D == 1) CALL(T, 1, V); else if (D == 2) CALL(T, 2, V); else CALL(T, 3, V); } while (0)
-    if (dtype == PF_F32) { if (g.vec == 4) CALL_D(float, 4); else CALL_D(float, 1); }
-    else if (dtype == PF_F64) { if (g.vec == 4) CALL_D(double, 4); else CALL_D(double, 1); }
-    else return PF_EINVAL;
-#undef CALL_D
-#undef CALL
-    PF_CHECK_LAUNCH();
-    return PF_OK;
+    return with_dtype(dtype, [&](auto t) {
+        return with_vec(g.vec, [&](auto v) {
+            return with_d3(D, [&](auto d) {
+                using T = decltype(t);
+                hipLaunchKernelGGL((k_debug_normals<T, decltype(d)::value, decltype(v)::value>), grid, dim3(PF_BLOCK), 0, st, seed, step0,
+                                   (T*)out, N, (int)B);
+                return launch_status();
+            });
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2420,16 +2386,138 @@ static FusedArgs<T> make_fused_args(const pf_filter_args* A, const Geom& g, cons
     return a;
 }
 
+// A run's observed flags: the caller's host array (A->observed), the caller's device array (A->observed_dev), or - neither given -
+// derived from y on the device into the workspace slot at off_ctr + 64 (runs of <= PF_AUTO_FLAGS steps); a run of ONE step on a
+// shared observation row (the online move) has its kernels look at the row itself instead: no launch derives a flag byte
+template <typename T>
+struct ObsFlags {
+    const uint8_t* host;  // A->observed
+    const uint8_t* dev;   // the flags the kernels read on the device, indexed by the absolute step (null: host or inline)
+    bool inline_y;        // the kernels read the flag off y (FusedArgs::obs = -2, ColumnRun::inline_y)
+    bool derive;          // dev is the workspace slot: a launch of the route derives it (launch_derive / launch_zero)
+    uint8_t* slot;
+    int64_t row;          // elements of y per step
+    const T* y;           // (derive) the run's first observation row
+
+    ObsFlags(const pf_filter_args* A, const WsLayout& wl, int64_t t0, int64_t n_steps) {
+        const bool none = !A->observed && !A->observed_dev && n_steps > 0;
+        host = A->observed;
+        inline_y = none && n_steps == 1 && A->y_rows == 1;
+        derive = none && !inline_y;
+        slot = (uint8_t*)A->ws + wl.off_ctr + 64;
+        row = A->y_rows * (int64_t)A->model.obs_dim;
+        y = derive ? (const T*)A->y + t0 * row : nullptr;
+        dev = derive ? slot - t0 : A->observed_dev;
+    }
+    // FusedArgs::obs of step t
+    int obs(int64_t t) const { return inline_y ? -2 : dev ? -1 : (host[t] != 0); }
+    // the derivation in a launch of its own: one wave per step
+    void launch_derive(int64_t n_steps, hipStream_t st) const {
+        hipLaunchKernelGGL((k_observed_flags<T>), dim3((unsigned)n_steps), dim3(PF_WAVE), 0, st, y, row, slot);
+    }
+    // clears `words` words at p - with `flags`, the derivation rides along: one launch (a kernel, not hipMemsetAsync: captured as a
+    // memset node the fill stopped clearing these records after ~195 replays of the same executable graph on ROCm 7.2 - every
+    // log-likelihood of the run came back NaN, "poisoned" - tools/graph_replays.py)
+    void launch_zero(uint32_t* p, size_t words, bool flags, int64_t n_steps, hipStream_t st) const {
+        const unsigned zb = (unsigned)((words + PF_BLOCK - 1) / PF_BLOCK);
+        if (flags)
+            hipLaunchKernelGGL((k_zero_and_flags<T>), dim3(zb + (unsigned)n_steps), dim3(PF_BLOCK), 0, st, p, words, zb, y, row, slot);
+        else
+            hipLaunchKernelGGL((k_zero_words<uint32_t>), dim3(zb), dim3(PF_BLOCK), 0, st, p, words);
+    }
+    // a persistent launch's piece (pf_column.hpp, pf_cluster.hpp): up to 32 * PFC_OBS_WORDS steps from the absolute step t
+    ColumnRun piece(int64_t t, int64_t left) const {
+        ColumnRun r;
+        r.t0 = (int)t;
+        r.n_steps = (int)(left < 32 * PFC_OBS_WORDS ? left : 32 * PFC_OBS_WORDS);
+        r.use_bits = (dev == nullptr && !inline_y) ? 1 : 0;
+        r.inline_y = inline_y ? 1 : 0;
+        for (int w = 0; w < PFC_OBS_WORDS; ++w) r.obs_bits[w] = 0u;
+        if (r.use_bits)
+            for (int q = 0; q < r.n_steps; ++q)
+                if (host[r.t0 + q]) r.obs_bits[q >> 5] |= 1u << (q & 31);
+        return r;
+    }
+};
+
+// pf_filter_run_timed: HIP events on the caller's stream around a route's timed window (none without kernel_ms), released on every path
+struct KernelTimer {
+    float* kernel_ms;
+    hipStream_t st;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool failed = false;  // hipEventCreate failed: the route returns rc
+    int rc = PF_OK;
+    KernelTimer(float* kernel_ms_, hipStream_t st_) : kernel_ms(kernel_ms_), st(st_) {
+        if (!kernel_ms) return;
+        for (auto& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) {
+                failed = true;
+                rc = (int)hipGetLastError();
+                return;
+            }
+        (void)hipEventRecord(ev[0], st);
+    }
+    ~KernelTimer() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void stop() const {
+        if (kernel_ms) (void)hipEventRecord(ev[1], st);
+    }
+    // waits for the stream: kernel_ms[0] = kernel_ms[2] = the window per time step, kernel_ms[1] = 0 (the planning kernel of
+    // earlier versions: folded into the step kernel's prologue)
+    int finish(int64_t n_steps) const {
+        if (!kernel_ms) return PF_OK;
+        const hipError_t se = hipStreamSynchronize(st);
+        if (se != hipSuccess) return (int)se;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        kernel_ms[0] = kernel_ms[2] = n_steps > 0 ? ms / (float)n_steps : 0.f;
+        kernel_ms[1] = 0.f;
+        return PF_OK;
+    }
+};
+
+// The persistent routes' folded instantiations (pf_column.hpp / pf_cluster.hpp: KIND / FILT / PROP): a run on Philox normals of one
+// of the model kinds KINDS calls f(kind, filter, proposal) - each a std::integral_constant - and returns true; any other run calls
+// nothing and returns false.  A kind comes with its observations and proposals: the Verhulst process with stochastic-volatility
+// observations and Bootstrap, every other kind with linear observations and Bootstrap or LGO.
+template <int... KINDS, typename F>
+static bool with_folded(const pf_filter_args* A, F&& f) {
+    bool hit = false;
+    auto with_kind = [&](auto kind_c) {
+        constexpr bool SV = decltype(kind_c)::value == PF_HID_VERHULST_EM;
+        if (hit || A->model.hid_kind != decltype(kind_c)::value || A->model.obs_kind != (SV ? PF_OBS_SV : PF_OBS_LINEAR)) return;
+        if (A->proposal != PF_PROP_BOOTSTRAP && (SV || A->proposal != PF_PROP_LGO)) return;
+        hit = true;
+        auto with_prop = [&](auto filt_c) {
+            if constexpr (!SV) {
+                if (A->proposal == PF_PROP_LGO) return f(kind_c, filt_c, int_c<PF_PROP_LGO>{});
+            }
+            f(kind_c, filt_c, int_c<PF_PROP_BOOTSTRAP>{});
+        };
+        if (A->filter == PF_FILTER_APF) with_prop(int_c<PF_FILTER_APF>{});
+        else with_prop(int_c<PF_FILTER_SISR>{});
+    };
+    if (!A->z_tape) (with_kind(int_c<KINDS>{}), ...);
+    return hit;
+}
+
 // Columns of fewer tiles than this keep their books inline (the column's last step workgroup, after its own work).  Since
 // the bookkeepers are dispatched LAST (the grid's slowest axis is the tile index, see below) they cost nothing on the critical path and inline lost at every
 // shape measured, single-tile columns included (1 024 x 8 192: 65.5 -> 59.1 us per step; 256 x 8 192 27.3 -> 22.1;
 // profiles/r04c_step_kernel_book_inline_threshold_ab.txt): 1 = never.  (Round 2's rule was 8.)
 #define PF_BOOK_INLINE_TILES 1
+// The per-step route of one arithmetic type / state dimension / vector width / tile geometry: declared in every unit, defined in the
+// units that compile k_fused_step kernels and instantiated (below) only in the one that owns it - see the translation-unit note above
 template <typename T, int D, int VEC, bool MULTI>
-static int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps,
-                           int finalize, hipStream_t st, float* kernel_ms) {
+int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize,
+                    hipStream_t st, float* kernel_ms);
+#ifdef PF_TU_STEP
+template <typename T, int D, int VEC, bool MULTI>
+int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize,
+                    hipStream_t st, float* kernel_ms) {
     FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
-    const uint8_t* observed = A->observed;  // host array
 
     const dim3 grid_tiles(g.tiles, g.B), block(PF_BLOCK);
     // the step kernel: one workgroup per tile + one bookkeeper per column, dispatched after all step workgroups
@@ -2450,25 +2538,11 @@ static int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayou
         a.kmap = 7u | ((q - 3u) << 8) | (3u << 16);
     }
     const dim3 grid(g.B, g.tiles + (a.book_inline ? 0 : 1));
-    // neither flag array given: the flags are derived from y on the device, into the workspace (runs of <= PF_AUTO_FLAGS steps)
-    const bool auto_flags = !A->observed && !A->observed_dev && n_steps > 0;
-    // ... of ONE step on a shared observation row (the online move): every kernel looks at the row itself (FusedArgs::is_obs, -2) -
-    // no launch that derives a flag byte
-    const bool inline_flag = auto_flags && n_steps == 1 && A->y_rows == 1;
-    uint8_t* const auto_fl = (uint8_t*)A->ws + wl.off_ctr + 64;
-    const int64_t auto_row = A->y_rows * (int64_t)A->model.obs_dim;
+    const ObsFlags<T> flags(A, wl, t0, n_steps);
     if (t0 == 0) {
-        // fresh filter: no previous step to account for (column records + poison flags)
-        // (a kernel, not hipMemsetAsync: captured as a memset node the fill stopped clearing these records after ~195
-        // replays of the same executable graph on ROCm 7.2 - every log-likelihood of the run came back NaN, "poisoned" -
-        // tools/graph_replays.py)
+        // fresh filter: no previous step to account for (column records + poison flags); the derived flags ride along
         const size_t words = (wl.off_ctr - wl.off_stat) / sizeof(uint32_t);  // (256-byte aligned regions)
-        const unsigned zb = (unsigned)((words + PF_BLOCK - 1) / PF_BLOCK);
-        if (auto_flags && !inline_flag)  // (the flags ride along: one launch)
-            hipLaunchKernelGGL((k_zero_and_flags<T>), dim3(zb + (unsigned)n_steps), dim3(PF_BLOCK), 0, st,
-                               (uint32_t*)((char*)A->ws + wl.off_stat), words, zb, (const T*)A->y + t0 * auto_row, auto_row, auto_fl);
-        else
-            hipLaunchKernelGGL((k_zero_words<uint32_t>), dim3(zb), dim3(PF_BLOCK), 0, st, (uint32_t*)((char*)A->ws + wl.off_stat), words);
+        flags.launch_zero((uint32_t*)((char*)A->ws + wl.off_stat), words, flags.derive, n_steps, st);
     }
     // state history: slot pointers per launch (the kernels keep addressing "buffer step & 1 is read, the other written")
     const int64_t ring = A->ring >= 3 ? A->ring : 0;
@@ -2485,15 +2559,9 @@ static int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayou
     place(t0);
     // partials of the incoming state (afterwards every step kernel leaves the partials of the state it wrote)
     a.step = (int)t0;
-    const bool dev_flags = A->observed_dev != nullptr || auto_flags;  // the kernels read the flags themselves
-    a.obs_dev = A->observed_dev;
-    if (auto_flags && !inline_flag) {
-        if (t0 != 0)
-            hipLaunchKernelGGL((k_observed_flags<T>), dim3((unsigned)n_steps), dim3(PF_WAVE), 0, st, (const T*)A->y + t0 * auto_row, auto_row, auto_fl);
-        a.obs_dev = auto_fl - t0;  // (indexed by the absolute step)
-    }
-    const int flag_mode = inline_flag ? -2 : -1;
-    a.obs = n_steps > 0 ? (dev_flags ? flag_mode : (observed[t0] != 0)) : 0;
+    a.obs_dev = flags.dev;
+    if (flags.derive && t0 != 0) flags.launch_derive(n_steps, st);
+    a.obs = n_steps > 0 ? flags.obs(t0) : 0;
     a.obs_next = 0;
     // (pf_run_hints.resume: the previous call on this argument block ended with a SISR step that left the partials and local
     // scans of exactly this state in the workspace - the pass is redundant)
@@ -2579,19 +2647,14 @@ static int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayou
             launch_step_as(std::integral_constant<int, PF_PROP_LGO>{}, std::false_type{});
         }
     };
-    hipEvent_t ev_loop[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        // measurement variant: HIP events on the caller's stream around the whole step loop
-        for (auto& e : ev_loop)
-            if (hipEventCreate(&e) != hipSuccess) return (int)hipGetLastError();
-        (void)hipEventRecord(ev_loop[0], st);
-    }
+    const KernelTimer timer(kernel_ms, st);  // (around the whole step loop)
+    if (timer.failed) return timer.rc;
     for (int64_t s = 0; s < n_steps; ++s) {
         const int64_t t = t0 + s;
         a.step = (int)t;
         place(t);
-        a.obs = dev_flags ? flag_mode : (observed[t] != 0);
-        a.obs_next = (s + 1 < n_steps) ? (dev_flags ? -1 : (observed[t + 1] != 0)) : (prepare_next ? 1 : 0);
+        a.obs = flags.obs(t);
+        a.obs_next = (s + 1 < n_steps) ? flags.obs(t + 1) : (prepare_next ? 1 : 0);
 #ifdef PF_DEVTOOLS
         // stage cuts on ONE launch (the last but one step) when PF_DEBUG_CUT_AT_END is set: the state entering it is
         // valid, so per-dispatch PMC rows of that launch profile the stages on real data
@@ -2604,28 +2667,44 @@ static int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayou
         a.debug_cut = cut_all;
 #endif
     }
-    if (kernel_ms) (void)hipEventRecord(ev_loop[1], st);
+    timer.stop();
     if (finalize) {
         a.step = (int)(t0 + n_steps);
         a.obs = a.obs_next = 0;
         a.finalize_only = 1;
         hipLaunchKernelGGL((k_fused_book<T, D>), dim3(1, g.B), block, 0, st, a);
     }
-    if (kernel_ms) {
-        hipError_t se = hipStreamSynchronize(st);
-        if (se != hipSuccess) return (int)se;
-        float loop_ms = 0.f;
-        (void)hipEventElapsedTime(&loop_ms, ev_loop[0], ev_loop[1]);
-        for (auto& e : ev_loop) (void)hipEventDestroy(e);
-        // one kernel per step: the in-sequence time of a step IS the step kernel's launch-to-launch duration
-        const float per_step = n_steps > 0 ? loop_ms / (float)n_steps : 0.f;
-        kernel_ms[0] = per_step;
-        kernel_ms[1] = 0.f;  // (the planning kernel of earlier versions: folded into the step kernel's prologue)
-        kernel_ms[2] = per_step;
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PF_OK : (int)e;
+    // (one kernel per step: the in-sequence time of a step IS the step kernel's launch-to-launch duration)
+    if (const int rc = timer.finish(n_steps)) return rc;
+    return launch_status();
 }
+
+// explicit instantiations: each unit the leaves it owns; the main unit, which dispatches to them (filter_run_checked), sees the
+// declaration alone and compiles no k_fused_step kernel
+#define PF_LEAF_AT(T, D, VEC, MULTI) \
+    template int filter_run_impl<T, D, VEC, MULTI>(const pf_filter_args*, const Geom&, const WsLayout&, int64_t, int64_t, int, hipStream_t, float*);
+#ifdef PF_TU_MULTI
+#define PF_LEAF(T, D, VEC) PF_LEAF_AT(T, D, VEC, PF_TU_MULTI != 0)
+#else
+#define PF_LEAF(T, D, VEC) PF_LEAF_AT(T, D, VEC, false) PF_LEAF_AT(T, D, VEC, true)
+#endif
+#if !defined(PF_TU_NO_F32D1) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32DN_ONLY)
+#if !defined(PF_TU_VEC) || PF_TU_VEC == 4
+PF_LEAF(float, 1, 4)
+#endif
+#if !defined(PF_TU_VEC) || PF_TU_VEC == 1
+PF_LEAF(float, 1, 1)
+#endif
+#endif
+#if !defined(PF_TU_NO_F32DN) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32D1_ONLY)
+PF_LEAF(float, 2, 4) PF_LEAF(float, 3, 4) PF_LEAF(float, 2, 1) PF_LEAF(float, 3, 1)
+#endif
+#if !defined(PF_TU_NO_F64) && !defined(PF_TU_F32DN_ONLY) && !defined(PF_TU_F32D1_ONLY)
+PF_LEAF(double, 1, 4) PF_LEAF(double, 2, 4) PF_LEAF(double, 3, 4) PF_LEAF(double, 1, 1) PF_LEAF(double, 2, 1) PF_LEAF(double, 3, 1)
+#endif
+#undef PF_LEAF
+#undef PF_LEAF_AT
+#endif  // PF_TU_STEP
 
 // ---- the column-persistent route (pf_column.hpp): filters of a few hundred .. a few thousand particles -----------------
 // One launch per run (per PFC_OBS_WORDS * 32 steps): no reduce / bookkeeping launches, no per-column records.
@@ -2639,7 +2718,7 @@ static inline int column_threads(int64_t N, int vec) {
 // (pf_column.hpp: `ragged`).  D > 1 keeps the geometry's width.  The state's layout in HBM and the Philox addressing do not
 // depend on it.  (One particle per lane for ALIGNED columns measured <= 16 % faster below 512 filters x 256 particles and
 // up to 3x slower above: profiles/r03_column_vec1_vs_vec4.txt - not adopted.)
-static inline int column_vec(const pf_filter_args* /*A*/, const Geom& /*g*/) { return 4; }
+#define PF_COLUMN_VEC 4
 static inline size_t column_lds_bytes(int64_t N, int D, size_t tsize, int vec) {
     int64_t np2 = 64;
     while (np2 < N) np2 <<= 1;
@@ -2656,163 +2735,77 @@ static inline bool column_eligible(const pf_filter_args* A, const Geom& g, int64
     if (!finalize || n_steps < 1 || A->ring >= 3) return false;
     if (A->hints.route == PF_ROUTE_PER_STEP) return false;
     const int64_t max_n = A->hints.column_max_n > 0 ? A->hints.column_max_n : PF_COLUMN_MAX_N;
-    if (A->N > max_n || column_threads(A->N, column_vec(A, g)) > 1024) return false;
-    return column_lds_bytes(A->N, A->model.dim, A->dtype == PF_F64 ? 8 : 4, column_vec(A, g)) <= 64 * 1024;  // (the default dynamic-LDS limit)
+    if (A->N > max_n || column_threads(A->N, PF_COLUMN_VEC) > 1024) return false;
+    return column_lds_bytes(A->N, A->model.dim, A->dtype == PF_F64 ? 8 : 4, PF_COLUMN_VEC) <= 64 * 1024;  // (the default dynamic-LDS limit)
 }
 
-template <typename T, int D, int VEC>
+template <typename T, int D>
 static int column_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps,
                            hipStream_t st, float* kernel_ms) {
+    constexpr int VEC = PF_COLUMN_VEC;  // (four particles per lane whatever N: columns of N % 4 != 0 take the RAGGED instantiations)
     FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
     const int nt = column_threads(A->N, VEC);
     const size_t lds = column_lds_bytes(A->N, D, sizeof(T), VEC);
-    // observed flags: the host's (baked into the launch arguments), the caller's device array, or derived from y here
-    const bool auto_flags = !A->observed && !A->observed_dev;
-    const bool inline_y = auto_flags && n_steps == 1 && A->y_rows == 1;  // (the online move: the kernel looks at y itself)
-    a.obs_dev = A->observed_dev;
-    if (auto_flags && !inline_y) {
-        uint8_t* fl = (uint8_t*)A->ws + wl.off_ctr + 64;
-        const int64_t row = A->y_rows * (int64_t)A->model.obs_dim;
-        hipLaunchKernelGGL((k_observed_flags<T>), dim3((unsigned)n_steps), dim3(PF_WAVE), 0, st, (const T*)A->y + t0 * row, row, fl);
-        a.obs_dev = fl - t0;
-    }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        for (auto& e : ev)
-            if (hipEventCreate(&e) != hipSuccess) return (int)hipGetLastError();
-        (void)hipEventRecord(ev[0], st);
-    }
+    const ObsFlags<T> flags(A, wl, t0, n_steps);
+    a.obs_dev = flags.dev;
+    if (flags.derive) flags.launch_derive(n_steps, st);
+    const KernelTimer timer(kernel_ms, st);
+    if (timer.failed) return timer.rc;
+    // the folded instantiations: float, four particles per lane - scalar states of the closed-form models and of Verhulst + SV,
+    // Lorenz-63 on whole 4-vectors (any workgroup size: the 256- or the 1024-thread bound); PF_ROUTE_COLUMN_GENERIC keeps the
+    // run-time kernel (tests compare the two)
+    auto with_column_folded = [&](auto&& f) {
+        if (A->hints.route == PF_ROUTE_COLUMN_GENERIC) return false;
+        if constexpr (sizeof(T) == 4 && D == 1) return with_folded<PF_HID_LINEAR, PF_HID_SINE_EM, PF_HID_OU, PF_HID_VERHULST_EM>(A, f);
+        if constexpr (sizeof(T) == 4 && D == 3) return A->N % VEC == 0 && with_folded<PF_HID_LORENZ63_EM>(A, f);
+        return false;
+    };
     for (int64_t done = 0; done < n_steps;) {
-        ColumnRun r;
-        r.t0 = (int)(t0 + done);
-        r.n_steps = (int)((n_steps - done < 32 * PFC_OBS_WORDS) ? n_steps - done : 32 * PFC_OBS_WORDS);
-        r.use_bits = (a.obs_dev == nullptr && !inline_y) ? 1 : 0;
-        r.inline_y = inline_y ? 1 : 0;
-        for (int w = 0; w < PFC_OBS_WORDS; ++w) r.obs_bits[w] = 0u;
-        if (r.use_bits)
-            for (int q = 0; q < r.n_steps; ++q)
-                if (A->observed[r.t0 + q]) r.obs_bits[q >> 5] |= 1u << (q & 31);
+        const ColumnRun r = flags.piece(t0 + done, n_steps - done);
         a.step = r.t0;
-        bool spec_ok = false;  // a specialised instantiation exists for this run (see below)
-        if constexpr (sizeof(T) == 4 && D == 1 && VEC == 4) {
-            const int hk = A->model.hid_kind;
-            const bool generic_only = A->hints.route == PF_ROUTE_COLUMN_GENERIC;
-            const bool closed = A->model.obs_kind == PF_OBS_LINEAR && (hk == PF_HID_LINEAR || hk == PF_HID_SINE_EM || hk == PF_HID_OU) &&
-                                (A->proposal == PF_PROP_BOOTSTRAP || A->proposal == PF_PROP_LGO);
-            const bool sv = A->model.obs_kind == PF_OBS_SV && hk == PF_HID_VERHULST_EM && A->proposal == PF_PROP_BOOTSTRAP;
-            spec_ok = !A->z_tape && !generic_only && (closed || sv);  // (any workgroup size: the 256- or the 1024-thread bound)
-        }
-        if constexpr (sizeof(T) == 4 && D == 3 && VEC == 4) {  // Lorenz-63
-            spec_ok = A->N % VEC == 0 && !A->z_tape && A->hints.route != PF_ROUTE_COLUMN_GENERIC && A->model.obs_kind == PF_OBS_LINEAR &&
-                      A->model.hid_kind == PF_HID_LORENZ63_EM && (A->proposal == PF_PROP_BOOTSTRAP || A->proposal == PF_PROP_LGO);
-        }
-        trace_launch(r.t0, (int)sizeof(T), D, VEC, A->resampler == PF_RESAMPLE_MULTINOMIAL ? 1 : 0, A->proposal, spec_ok ? 1 : 0,
-                     /*SPEC*/ 9, spec_ok ? A->model.hid_kind : 0, 0);
-        const bool user = A->model.hid_kind == PF_HID_USER_AFFINE;
-        // columns of N % 4 != 0 particles (scalar states): the RAGGED instantiations
-        auto with_rag = [&](auto&& f) {
-            if constexpr (VEC == 4) {
-                if (A->N % VEC != 0) return f(std::true_type{});
-            }
-            f(std::false_type{});
-        };
-        auto launch = [&](auto tpb_c) {
-            constexpr int TPB = decltype(tpb_c)::value;
-            with_rag([&](auto rag_c) {
-                constexpr bool RAG = decltype(rag_c)::value;
-                if (user) hipLaunchKernelGGL((k_fused_column<T, D, VEC, TPB, true, -1, -1, -1, RAG>), dim3(g.B), dim3(nt), lds, st, a, r);
-                else hipLaunchKernelGGL((k_fused_column<T, D, VEC, TPB, false, -1, -1, -1, RAG>), dim3(g.B), dim3(nt), lds, st, a, r);
-            });
-        };
+        // k_fused_column with KIND / FILT / PROP folded (KIND = -1: the run-time kernel), at the 256- or the 1024-thread bound;
+        // columns of N % 4 != 0 particles take the RAGGED instantiations (the folded Lorenz-63 set has none)
         // (a 512-thread bound would lift the scratch of the D > 1 kernels - but at > 128 VGPRs only ONE 8-wave workgroup fits
         // a CU instead of two: 1024 x 2048 measured 33 us per step against 21)
-        // specialised instantiations (pf_column.hpp: KIND / FILT / PROP): float, built-in models, four particles per lane,
-        // <= 256 threads, Philox normals; PF_COLUMN_GENERIC=1 keeps the run-time kernel (tests compare the two)
-        bool specialised = false;
-        if constexpr (sizeof(T) == 4 && D == 1 && VEC == 4) {
-            const int hk = A->model.hid_kind;
-            if (spec_ok) {
-                specialised = true;
-                auto go = [&](auto kind_c, auto filt_c, auto prop_c) {
-                    with_rag([&](auto rag_c) {
-                        if (nt <= 256)
-                            hipLaunchKernelGGL((k_fused_column<T, D, VEC, 256, false, decltype(kind_c)::value, decltype(filt_c)::value,
-                                                               decltype(prop_c)::value, decltype(rag_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
-                        else
-                            hipLaunchKernelGGL((k_fused_column<T, D, VEC, 1024, false, decltype(kind_c)::value, decltype(filt_c)::value,
-                                                               decltype(prop_c)::value, decltype(rag_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
-                    });
-                };
-                auto with_prop = [&](auto kind_c, auto filt_c) {
-                    if (A->proposal == PF_PROP_LGO) go(kind_c, filt_c, std::integral_constant<int, PF_PROP_LGO>{});
-                    else go(kind_c, filt_c, std::integral_constant<int, PF_PROP_BOOTSTRAP>{});
-                };
-                auto with_filt = [&](auto kind_c) {
-                    if (A->filter == PF_FILTER_APF) with_prop(kind_c, std::integral_constant<int, PF_FILTER_APF>{});
-                    else with_prop(kind_c, std::integral_constant<int, PF_FILTER_SISR>{});
-                };
-                if (hk == PF_HID_LINEAR) with_filt(std::integral_constant<int, PF_HID_LINEAR>{});
-                else if (hk == PF_HID_SINE_EM) with_filt(std::integral_constant<int, PF_HID_SINE_EM>{});
-                else if (hk == PF_HID_OU) with_filt(std::integral_constant<int, PF_HID_OU>{});
-                else if (A->filter == PF_FILTER_APF)  // Verhulst + stochastic volatility: Bootstrap only
-                    go(std::integral_constant<int, PF_HID_VERHULST_EM>{}, std::integral_constant<int, PF_FILTER_APF>{}, std::integral_constant<int, PF_PROP_BOOTSTRAP>{});
-                else
-                    go(std::integral_constant<int, PF_HID_VERHULST_EM>{}, std::integral_constant<int, PF_FILTER_SISR>{}, std::integral_constant<int, PF_PROP_BOOTSTRAP>{});
-            }
+        auto launch = [&](auto user_c, auto kind_c, auto filt_c, auto prop_c) {
+            constexpr int KIND = decltype(kind_c)::value;
+            trace_launch(r.t0, (int)sizeof(T), D, VEC, A->resampler == PF_RESAMPLE_MULTINOMIAL ? 1 : 0, A->proposal, KIND >= 0 ? 1 : 0,
+                         /*SPEC*/ 9, KIND >= 0 ? KIND : 0, 0);
+            auto go = [&](auto tpb_c, auto rag_c) {
+                hipLaunchKernelGGL((k_fused_column<T, D, VEC, decltype(tpb_c)::value, decltype(user_c)::value, KIND, decltype(filt_c)::value,
+                                                   decltype(prop_c)::value, decltype(rag_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
+            };
+            auto with_rag = [&](auto tpb_c) {
+                if constexpr (KIND < 0 || D == 1) {
+                    if (A->N % VEC != 0) return go(tpb_c, std::true_type{});
+                }
+                go(tpb_c, std::false_type{});
+            };
+            if (nt <= 256) with_rag(int_c<256>{});
+            else with_rag(int_c<1024>{});
+        };
+        if (!with_column_folded([&](auto kind_c, auto filt_c, auto prop_c) { launch(std::false_type{}, kind_c, filt_c, prop_c); })) {
+            if (A->model.hid_kind == PF_HID_USER_AFFINE) launch(std::true_type{}, int_c<-1>{}, int_c<-1>{}, int_c<-1>{});
+            else launch(std::false_type{}, int_c<-1>{}, int_c<-1>{}, int_c<-1>{});
         }
-        if constexpr (sizeof(T) == 4 && D == 3 && VEC == 4) {
-            if (spec_ok) {
-                specialised = true;
-                auto go3 = [&](auto filt_c, auto prop_c) {  // (the 256- or - 1 024 < N <= 2 048 - the 1024-thread bound)
-                    if (nt <= 256)
-                        hipLaunchKernelGGL((k_fused_column<T, D, VEC, 256, false, PF_HID_LORENZ63_EM, decltype(filt_c)::value,
-                                                           decltype(prop_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
-                    else
-                        hipLaunchKernelGGL((k_fused_column<T, D, VEC, 1024, false, PF_HID_LORENZ63_EM, decltype(filt_c)::value,
-                                                           decltype(prop_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
-                };
-                auto with_prop3 = [&](auto filt_c) {
-                    if (A->proposal == PF_PROP_LGO) go3(filt_c, std::integral_constant<int, PF_PROP_LGO>{});
-                    else go3(filt_c, std::integral_constant<int, PF_PROP_BOOTSTRAP>{});
-                };
-                if (A->filter == PF_FILTER_APF) with_prop3(std::integral_constant<int, PF_FILTER_APF>{});
-                else with_prop3(std::integral_constant<int, PF_FILTER_SISR>{});
-            }
-        }
-        if (specialised) {
-        } else if (nt <= 256) launch(std::integral_constant<int, 256>{});
-        else launch(std::integral_constant<int, 1024>{});
         done += r.n_steps;
     }
-    if (kernel_ms) {
-        (void)hipEventRecord(ev[1], st);
-        hipError_t se = hipStreamSynchronize(st);
-        if (se != hipSuccess) return (int)se;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        kernel_ms[0] = kernel_ms[2] = ms / (float)n_steps;  // the run's one kernel, per time step
-        kernel_ms[1] = 0.f;
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PF_OK : (int)e;
+    timer.stop();
+    if (const int rc = timer.finish(n_steps)) return rc;  // (the run's one kernel, per time step)
+    return launch_status();
 }
-#define PF_COL_ARGS const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms
-int pf_run_column_f32(PF_COL_ARGS);
-int pf_run_column_f64(PF_COL_ARGS);
-#define PF_DEFINE_COLUMN(NAME, T)                                                                     \
-    int NAME(PF_COL_ARGS) {                                                                           \
-        const int D = A->model.dim;                                                                   \
-        /* four particles per lane whatever N: columns of N % 4 != 0 take the RAGGED instantiations */  \
-        if (D == 1) return column_run_impl<T, 1, 4>(A, g, wl, t0, n_steps, st, kernel_ms);            \
-        if (D == 2) return column_run_impl<T, 2, 4>(A, g, wl, t0, n_steps, st, kernel_ms);            \
-        return column_run_impl<T, 3, 4>(A, g, wl, t0, n_steps, st, kernel_ms);                        \
-    }
+// the route's entries, one per arithmetic type, each in the unit that compiles its kernels
+int pf_run_column_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms);
+int pf_run_column_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms);
 #if defined(PF_TU_COLUMN_F32) || !defined(PF_TU_SPLIT)
-PF_DEFINE_COLUMN(pf_run_column_f32, float)
+int pf_run_column_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms) {
+    return with_d3(A->model.dim, [&](auto d) { return column_run_impl<float, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms); });
+}
 #endif
 #if defined(PF_TU_COLUMN_F64) || !defined(PF_TU_SPLIT)
-PF_DEFINE_COLUMN(pf_run_column_f64, double)
+int pf_run_column_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms) {
+    return with_d3(A->model.dim, [&](auto d) { return column_run_impl<double, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms); });
+}
 #endif
 
 // ---- the column-cluster route (pf_cluster.hpp): filters of 2 049 .. 16 384 particles, c workgroups per filter, one launch per
@@ -2866,18 +2859,12 @@ template <typename K> static inline int cluster_slots(K kernel, size_t lds) {
 }
 template <typename T, int D>
 static int cluster_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps,
-                            hipStream_t st, float* kernel_ms) {
+                            hipStream_t st, float* kernel_ms, ThetaFold* theta) {
     constexpr int VEC = PFK_HOST_VEC;
     FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
     const size_t lds = cluster_lds_bytes(D, sizeof(T));
-    const bool auto_flags = !A->observed && !A->observed_dev;
-    a.obs_dev = A->observed_dev;
-    uint8_t* const auto_fl = (uint8_t*)A->ws + wl.off_ctr + 64;
-    const int64_t auto_row = A->y_rows * (int64_t)A->model.obs_dim;
-    // one-step runs on a shared observation row: the kernel reads the flag off y itself (ColumnRun::inline_y)
-    const bool inline_y = auto_flags && n_steps == 1 && A->y_rows == 1;
-    bool flags_pending = auto_flags && !inline_y;  // (derived by the launch that clears the first piece's records: k_zero_and_flags)
-    if (auto_flags && !inline_y) a.obs_dev = auto_fl - t0;
+    const ObsFlags<T> flags(A, wl, t0, n_steps);  // (derived by the launch that clears the first piece's records: k_zero_and_flags)
+    a.obs_dev = flags.dev;
     // the caller numbers its launches (pf_run_hints.cluster_generation): tagged records, nothing to clear
     bool numbered = A->hints.cluster_generation != 0 && A->status != nullptr && n_steps <= 32 * PFC_OBS_WORDS;
     if (numbered) {
@@ -2887,45 +2874,11 @@ static int cluster_run_impl(const pf_filter_args* A, const Geom& g, const WsLayo
     }
     const int c = (int)((A->N + PFK_TPB * VEC - 1) / (PFK_TPB * VEC));
     const int nchunks = (int)((A->N + 64 * VEC - 1) / (64 * VEC));
-    // which instantiation: float runs of the built-in scalar closed-form models on Philox normals take KIND / FILT / PROP folded
-    // (as on the column route), everything else the run-time kernel
-    bool spec_ok = false;
-    if constexpr (sizeof(T) == 4 && D == 1) {
-        const int hk = A->model.hid_kind;
-        spec_ok = !A->z_tape && A->model.obs_kind == PF_OBS_LINEAR &&
-                  (hk == PF_HID_LINEAR || hk == PF_HID_SINE_EM || hk == PF_HID_OU) &&
-                  (A->proposal == PF_PROP_BOOTSTRAP || A->proposal == PF_PROP_LGO);
-    }
-    auto with_kernel = [&](auto&& f) {
-        if constexpr (sizeof(T) == 4 && D == 1) {
-            if (spec_ok) {
-                auto with_prop = [&](auto kind_c, auto filt_c) {
-                    if (A->proposal == PF_PROP_LGO)
-                        f(k_fused_cluster<T, D, VEC, decltype(kind_c)::value, decltype(filt_c)::value, PF_PROP_LGO>);
-                    else
-                        f(k_fused_cluster<T, D, VEC, decltype(kind_c)::value, decltype(filt_c)::value, PF_PROP_BOOTSTRAP>);
-                };
-                auto with_filt = [&](auto kind_c) {
-                    if (A->filter == PF_FILTER_APF) with_prop(kind_c, std::integral_constant<int, PF_FILTER_APF>{});
-                    else with_prop(kind_c, std::integral_constant<int, PF_FILTER_SISR>{});
-                };
-                const int hk = A->model.hid_kind;
-                if (hk == PF_HID_LINEAR) with_filt(std::integral_constant<int, PF_HID_LINEAR>{});
-                else if (hk == PF_HID_SINE_EM) with_filt(std::integral_constant<int, PF_HID_SINE_EM>{});
-                else with_filt(std::integral_constant<int, PF_HID_OU>{});
-                return;
-            }
-        }
-        f(k_fused_cluster<T, D, VEC, -1, -1, -1>);
-    };
     int rc = PF_OK;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        for (auto& e : ev)
-            if (hipEventCreate(&e) != hipSuccess) return (int)hipGetLastError();
-        (void)hipEventRecord(ev[0], st);
-    }
-    with_kernel([&](auto kernel) {
+    const KernelTimer timer(kernel_ms, st);
+    if (timer.failed) return timer.rc;
+    // the run on one instantiation of k_fused_cluster: KIND = -1 the run-time kernel, else the folded one
+    auto run = [&](auto kernel, int kind) {
         // (nothing has been launched yet: PF_CLUSTER_INFEASIBLE sends the caller - filter_run_checked - to the per-step route)
         if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             (void)hipGetLastError();
@@ -2941,29 +2894,16 @@ static int cluster_run_impl(const pf_filter_args* A, const Geom& g, const WsLayo
         }
         unsigned char* clu = (unsigned char*)A->ws + wl.off_clu;
         for (int64_t done = 0; done < n_steps;) {
-            ColumnRun r;
-            r.t0 = (int)(t0 + done);
-            r.n_steps = (int)((n_steps - done < 32 * PFC_OBS_WORDS) ? n_steps - done : 32 * PFC_OBS_WORDS);
-            r.use_bits = (a.obs_dev == nullptr && !inline_y) ? 1 : 0;
-            r.inline_y = inline_y ? 1 : 0;
-            for (int w = 0; w < PFC_OBS_WORDS; ++w) r.obs_bits[w] = 0u;
-            if (r.use_bits)
-                for (int q = 0; q < r.n_steps; ++q)
-                    if (A->observed[r.t0 + q]) r.obs_bits[q >> 5] |= 1u << (q & 31);
+            const ColumnRun r = flags.piece(t0 + done, n_steps - done);
             a.step = r.t0;
             // fresh tags for this piece: error word + every record of the batch (a kernel, not a memset node - see k_zero_words)
             // (only what this instantiation's records occupy: NG granule rows of 1 KB per column and parity, after the error word)
             const size_t ng = ((size_t)(5 + 2 * D) * (sizeof(T) / 4) + 2 + 2) / 3;
             size_t words = (256 + (size_t)2 * g.B * PF_CLUSTER_NG * 64 * 16) / sizeof(uint32_t);
             if (g.B <= per_launch) words = (256 + (size_t)2 * g.B * ng * 64 * 16) / sizeof(uint32_t);  // (one group: its block is compact)
-            const unsigned zb = (unsigned)((words + PF_BLOCK - 1) / PF_BLOCK);
-            if (flags_pending)
-                hipLaunchKernelGGL((k_zero_and_flags<T>), dim3(zb + (unsigned)n_steps), dim3(PF_BLOCK), 0, st, (uint32_t*)clu, words, zb,
-                                   (const T*)A->y + t0 * auto_row, auto_row, auto_fl);
-            else if (!numbered)
-                hipLaunchKernelGGL((k_zero_words<uint32_t>), dim3(zb), dim3(PF_BLOCK), 0, st, (uint32_t*)clu, words);
-            flags_pending = false;
-            trace_launch(r.t0, (int)sizeof(T), D, VEC, 0, A->proposal, spec_ok ? 1 : 0, /*SPEC*/ 10, spec_ok ? A->model.hid_kind : 0, c);
+            const bool with_flags = flags.derive && done == 0;
+            if (with_flags || !numbered) flags.launch_zero((uint32_t*)clu, words, with_flags, n_steps, st);
+            trace_launch(r.t0, (int)sizeof(T), D, VEC, 0, A->proposal, kind >= 0 ? 1 : 0, /*SPEC*/ 10, kind >= 0 ? kind : 0, c);
             for (int b0 = 0; b0 < g.B; b0 += per_launch) {
                 ClusterRun cr;
                 cr.b0 = b0;
@@ -2978,148 +2918,68 @@ static int cluster_run_impl(const pf_filter_args* A, const Geom& g, const WsLayo
                 cr.patience = A->hints.cluster_patience != 0 ? A->hints.cluster_patience : PFK_SPIN_LIMIT;
                 cr.spread = A->hints.route == PF_ROUTE_CLUSTER_SPREAD ? 1 : 0;
                 cr.th = ClusterTheta{};
-                if (tls_theta_fold != nullptr && g.B <= per_launch && done + r.n_steps == n_steps && done == 0) {
+                if (theta != nullptr && g.B <= per_launch && done + r.n_steps == n_steps && done == 0) {
                     // (one launch carries the whole run and every column: its last column to finish does the theta update)
-                    ThetaFold* tf = tls_theta_fold;
                     cr.th.enabled = 1;
-                    cr.th.w = tf->w;
-                    cr.th.ll = tf->ll;
-                    cr.th.stats = tf->stats;
-                    cr.th.slot = (double*)tf->slot;
-                    cr.th.seq = (unsigned long long)tf->seq;
-                    cr.th.acc = tf->acc;
+                    cr.th.w = theta->w;
+                    cr.th.ll = theta->ll;
+                    cr.th.stats = theta->stats;
+                    cr.th.slot = (double*)theta->slot;
+                    cr.th.seq = (unsigned long long)theta->seq;
+                    cr.th.acc = theta->acc;
                     cr.th.arrive = (unsigned*)clu + 16;
-                    tf->folded = 1;
+                    theta->folded = 1;
                 }
                 cr.rec = clu + 256 + (size_t)b0 * 2 * PF_CLUSTER_NG * 64 * 16;  // (this group's [2][nb][NG][64] block)
                 hipLaunchKernelGGL(kernel, dim3((unsigned)(cr.nbp * c)), dim3(PFK_TPB), lds, st, a, r, cr);
             }
             done += r.n_steps;
         }
-    });
-    if (rc != PF_OK) {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        return rc;
-    }
-    if (kernel_ms) {
-        (void)hipEventRecord(ev[1], st);
-        hipError_t se = hipStreamSynchronize(st);
-        if (se != hipSuccess) return (int)se;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        kernel_ms[0] = kernel_ms[2] = ms / (float)n_steps;
-        kernel_ms[1] = 0.f;
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PF_OK : (int)e;
+    };
+    // float runs of the built-in scalar closed-form models take KIND / FILT / PROP folded (as on the column route)
+    bool folded = false;
+    if constexpr (sizeof(T) == 4 && D == 1)
+        folded = with_folded<PF_HID_LINEAR, PF_HID_SINE_EM, PF_HID_OU>(A, [&](auto kind_c, auto filt_c, auto prop_c) {
+            run(k_fused_cluster<T, D, VEC, decltype(kind_c)::value, decltype(filt_c)::value, decltype(prop_c)::value>, decltype(kind_c)::value);
+        });
+    if (!folded) run(k_fused_cluster<T, D, VEC, -1, -1, -1>, -1);
+    if (rc != PF_OK) return rc;
+    timer.stop();
+    if ((rc = timer.finish(n_steps)) != PF_OK) return rc;
+    return launch_status();
 }
-int pf_run_cluster_f32(PF_COL_ARGS);
-int pf_run_cluster_f64(PF_COL_ARGS);
-#define PF_DEFINE_CLUSTER(NAME, T)                                                        \
-    int NAME(PF_COL_ARGS) {                                                               \
-        const int D = A->model.dim;                                                       \
-        if (D == 1) return cluster_run_impl<T, 1>(A, g, wl, t0, n_steps, st, kernel_ms);  \
-        if (D == 2) return cluster_run_impl<T, 2>(A, g, wl, t0, n_steps, st, kernel_ms);  \
-        return cluster_run_impl<T, 3>(A, g, wl, t0, n_steps, st, kernel_ms);              \
-    }
+int pf_run_cluster_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
+                       ThetaFold* theta);
+int pf_run_cluster_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
+                       ThetaFold* theta);
 #if defined(PF_TU_CLUSTER_F32) || !defined(PF_TU_SPLIT)
-PF_DEFINE_CLUSTER(pf_run_cluster_f32, float)
+int pf_run_cluster_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
+                       ThetaFold* theta) {
+    return with_d3(A->model.dim, [&](auto d) { return cluster_run_impl<float, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms, theta); });
+}
 #endif
 #if defined(PF_TU_CLUSTER_F64) || !defined(PF_TU_SPLIT)
-PF_DEFINE_CLUSTER(pf_run_cluster_f64, double)
-#endif
-
-// one entry per arithmetic type / state dimension / vector width / tile geometry (see the translation-unit note above)
-#define PF_RUN_ARGS const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize, \
-                    hipStream_t st, float* kernel_ms
-#define PF_RUN_PASS A, g, wl, t0, n_steps, finalize, st, kernel_ms
-int pf_run_f32(PF_RUN_ARGS);
-int pf_run_f64(PF_RUN_ARGS);
-#define PF_DECLARE_LEAVES(SFX)            \
-    int pf_run_f32_d1_v4##SFX(PF_RUN_ARGS); \
-    int pf_run_f32_d1_v1##SFX(PF_RUN_ARGS); \
-    int pf_run_f32_dn##SFX(PF_RUN_ARGS);    \
-    int pf_run_f64##SFX(PF_RUN_ARGS);
-PF_DECLARE_LEAVES(_m0)
-PF_DECLARE_LEAVES(_m1)
-#ifndef PF_TU_NO_API
-int pf_run_f32(PF_RUN_ARGS) {
-    const bool multi = g.rounds_per_tile > 1;
-    if (A->model.dim != 1) return multi ? pf_run_f32_dn_m1(PF_RUN_PASS) : pf_run_f32_dn_m0(PF_RUN_PASS);
-    if (g.vec == 4) return multi ? pf_run_f32_d1_v4_m1(PF_RUN_PASS) : pf_run_f32_d1_v4_m0(PF_RUN_PASS);
-    return multi ? pf_run_f32_d1_v1_m1(PF_RUN_PASS) : pf_run_f32_d1_v1_m0(PF_RUN_PASS);
-}
-int pf_run_f64(PF_RUN_ARGS) {
-    return g.rounds_per_tile > 1 ? pf_run_f64_m1(PF_RUN_PASS) : pf_run_f64_m0(PF_RUN_PASS);
+int pf_run_cluster_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
+                       ThetaFold* theta) {
+    return with_d3(A->model.dim, [&](auto d) { return cluster_run_impl<double, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms, theta); });
 }
 #endif
-#define RUN(T, DD, V, MULTI) return filter_run_impl<T, DD, V, MULTI>(PF_RUN_PASS);
-#define RUN_D(T, V, MULTI) \
-    if (D == 1) { RUN(T, 1, V, MULTI) } else if (D == 2) { RUN(T, 2, V, MULTI) } else { RUN(T, 3, V, MULTI) }
-#define PF_DEFINE_D1_V4(SFX, MULTI) int pf_run_f32_d1_v4##SFX(PF_RUN_ARGS) { RUN(float, 1, 4, MULTI) }
-#define PF_DEFINE_D1_V1(SFX, MULTI) int pf_run_f32_d1_v1##SFX(PF_RUN_ARGS) { RUN(float, 1, 1, MULTI) }
-#define PF_DEFINE_DN(SFX, MULTI)                                              \
-    int pf_run_f32_dn##SFX(PF_RUN_ARGS) {                                     \
-        const int D = A->model.dim;                                           \
-        if (g.vec == 4) {                                                     \
-            if (D == 2) { RUN(float, 2, 4, MULTI) } else { RUN(float, 3, 4, MULTI) } \
-        } else {                                                              \
-            if (D == 2) { RUN(float, 2, 1, MULTI) } else { RUN(float, 3, 1, MULTI) } \
-        }                                                                     \
-    }
-#define PF_DEFINE_F64(SFX, MULTI)                                    \
-    int pf_run_f64##SFX(PF_RUN_ARGS) {                               \
-        const int D = A->model.dim;                                  \
-        if (g.vec == 4) { RUN_D(double, 4, MULTI) } else { RUN_D(double, 1, MULTI) } \
-    }
-#if !defined(PF_TU_MULTI) || PF_TU_MULTI == 0
-#define PF_FOR_M0(X) X(_m0, false)
-#else
-#define PF_FOR_M0(X)
-#endif
-#if !defined(PF_TU_MULTI) || PF_TU_MULTI == 1
-#define PF_FOR_M1(X) X(_m1, true)
-#else
-#define PF_FOR_M1(X)
-#endif
-#if !defined(PF_TU_NO_F32D1) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32DN_ONLY)
-#if !defined(PF_TU_VEC) || PF_TU_VEC == 4
-PF_FOR_M0(PF_DEFINE_D1_V4)
-PF_FOR_M1(PF_DEFINE_D1_V4)
-#endif
-#if !defined(PF_TU_VEC) || PF_TU_VEC == 1
-PF_FOR_M0(PF_DEFINE_D1_V1)
-PF_FOR_M1(PF_DEFINE_D1_V1)
-#endif
-#endif
-#if !defined(PF_TU_NO_F32DN) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32D1_ONLY)
-PF_FOR_M0(PF_DEFINE_DN)
-PF_FOR_M1(PF_DEFINE_DN)
-#endif
-#if !defined(PF_TU_NO_F64) && !defined(PF_TU_F32DN_ONLY) && !defined(PF_TU_F32D1_ONLY)
-PF_FOR_M0(PF_DEFINE_F64)
-PF_FOR_M1(PF_DEFINE_F64)
-#endif
-#undef RUN_D
-#undef RUN
+
 
 #ifndef PF_TU_NO_API
+// theta: pf_filter_observe's theta update, which the cluster route folds into its launch (null: none)
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
-                              float* kernel_ms);
+                              float* kernel_ms, ThetaFold* theta);
 
 extern "C" int pf_filter_run(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream) {
-    return filter_run_checked(A, t0, n_steps, finalize, stream, nullptr);
+    return filter_run_checked(A, t0, n_steps, finalize, stream, nullptr, nullptr);
 }
 
 extern "C" int pf_filter_observe(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* w, const void* ll, void* stats,
                                  void* host_slot, uint64_t seq, void* acc, void* stream) {
     if (!A || !w || !ll || !stats || ((uintptr_t)host_slot & 7) != 0) return PF_EINVAL;
     ThetaFold tf{w, ll, stats, host_slot, seq, acc, 0};
-    tls_theta_fold = &tf;
-    const int rc = filter_run_checked(A, t0, n_steps, finalize, stream, nullptr);
-    tls_theta_fold = nullptr;
+    const int rc = filter_run_checked(A, t0, n_steps, finalize, stream, nullptr, &tf);
     if (rc != PF_OK) return rc;
     if (tf.folded) return PF_OK;  // (the column-cluster launch did the update itself)
     return pf_theta_step(w, ll, A->B, A->dtype, stats, host_slot, seq, acc, A->status, stream);
@@ -3128,7 +2988,7 @@ extern "C" int pf_filter_observe(const pf_filter_args* A, int64_t t0, int64_t n_
 extern "C" int pf_filter_run_timed(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
                                    float* kernel_ms) {
     if (!kernel_ms) return PF_EINVAL;
-    return filter_run_checked(A, t0, n_steps, finalize, stream, kernel_ms);
+    return filter_run_checked(A, t0, n_steps, finalize, stream, kernel_ms, nullptr);
 }
 
 // ---- hipGraph variant: the whole launch sequence of a run captured once, replayed with one host call -----------------
@@ -3152,7 +3012,7 @@ extern "C" int pf_filter_graph_create(const pf_filter_args* A, int64_t t0, int64
         (void)hipStreamDestroy(st);
         return (int)e;
     }
-    const int rc = filter_run_checked(A, t0, n_steps, finalize, (void*)st, nullptr);
+    const int rc = filter_run_checked(A, t0, n_steps, finalize, (void*)st, nullptr, nullptr);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(st, &graph);
     (void)hipStreamDestroy(st);
@@ -3188,7 +3048,7 @@ extern "C" int pf_filter_graph_destroy(void* handle) {
 }
 
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
-                              float* kernel_ms) {
+                              float* kernel_ms, ThetaFold* theta) {
     if (!A || A->struct_size != sizeof(pf_filter_args)) return PF_EINVAL;  // (another ABI version: include/pf_amd.h)
     if (A->hints.route < 0 || A->hints.route > PF_ROUTE_CLUSTER_SPREAD || A->hints.column_max_n < 0 || A->hints.tile_target < 0 ||
         A->hints.cluster_patience < -1 || A->hints.cluster_patience > (1 << 30) || A->hints.cluster_generation < 0)
@@ -3214,13 +3074,13 @@ static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_ste
     if (A->filter != PF_FILTER_SISR && A->filter != PF_FILTER_APF) return PF_EUNSUPPORTED;
     if (!A->pos) return PF_EINVAL;
     const Geom g = make_geom(A->N, A->B, A->hints.tile_target);
-    const WsLayout wl = make_ws(g, PF_MAXD);
+    const WsLayout wl = make_ws(g);
     if (A->ws_bytes < wl.total) return PF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (!column_eligible(A, g, n_steps, finalize) && cluster_eligible(A, g, n_steps, finalize) && wl.clu_bytes != 0) {
         if (A->dtype != PF_F32 && A->dtype != PF_F64) return PF_EINVAL;
-        rc = A->dtype == PF_F32 ? pf_run_cluster_f32(A, g, wl, t0, n_steps, st, kernel_ms)
-                                : pf_run_cluster_f64(A, g, wl, t0, n_steps, st, kernel_ms);
+        rc = A->dtype == PF_F32 ? pf_run_cluster_f32(A, g, wl, t0, n_steps, st, kernel_ms, theta)
+                                : pf_run_cluster_f64(A, g, wl, t0, n_steps, st, kernel_ms, theta);
         if (rc != PF_CLUSTER_INFEASIBLE) return rc;  // (else: no slot for one filter's workgroups / LDS refused - the per-step route)
     }
     if (column_eligible(A, g, n_steps, finalize)) {
@@ -3228,8 +3088,15 @@ static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_ste
         if (A->dtype == PF_F64) return pf_run_column_f64(A, g, wl, t0, n_steps, st, kernel_ms);
         return PF_EINVAL;
     }
-    if (A->dtype == PF_F32) return pf_run_f32(A, g, wl, t0, n_steps, finalize, st, kernel_ms);
-    if (A->dtype == PF_F64) return pf_run_f64(A, g, wl, t0, n_steps, finalize, st, kernel_ms);
-    return PF_EINVAL;
+    return with_dtype(A->dtype, [&](auto t) {  // the per-step route's leaf (filter_run_impl's explicit instantiations)
+        return with_d3(A->model.dim, [&](auto d) {
+            return with_vec(g.vec, [&](auto v) {
+                return with_bool(g.rounds_per_tile > 1, [&](auto multi) {
+                    return filter_run_impl<decltype(t), decltype(d)::value, decltype(v)::value, decltype(multi)::value>(A, g, wl, t0, n_steps,
+                                                                                                                  finalize, st, kernel_ms);
+                });
+            });
+        });
+    });
 }
 #endif  // !PF_TU_NO_API
