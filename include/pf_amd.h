@@ -274,6 +274,38 @@ int pf_host_free(void* p);
  * resampling.py:24-52 with the uniform u in [0, 1]): ancestors (B, int64).  cdf_scratch: B values of `dtype`. */
 int pf_theta_resample(const void* logw, int64_t B, double u, int dtype, int64_t* ancestors, void* cdf_scratch, void* stream);
 
+/* The parameter mutation of NESS, the nested particle filter (pyfilter/inference/sequential/ness.py:50-58 -> kernels/online.py:29-45
+ * `OnlineKernel.update`): after pf_theta_resample the jittering kernel is fitted to the weighted theta-particles and every particle
+ * moves to its ancestor's location plus std * eps - two launches instead of the several dozen of the torch operations (a sort per
+ * parameter, cumsum, two argmin, gathers, diag, masked writes, the bijections).  Kernel families (kernels/jittering.py:141-225): */
+#define PF_JITTER_NONSHRINKING 0 /* NonShrinkingKernel: location x[anc], scale bw * sqrt(robust var), bw = clamp(1.59 ess^-1/3)    */
+#define PF_JITTER_SHRINKING 1    /* ShrinkingKernel:    location mean + sqrt(1 - bw^2) (x[anc] - mean), the same scale             */
+#define PF_JITTER_LIUWEST 2      /* LiuWestShrinkage(a = par): location a x[anc] + (1 - a) mean, scale sqrt(1 - a^2) sqrt(var)     */
+#define PF_JITTER_CONSTANT 3     /* ConstantKernel(scale = par, or one value per parameter): location x[anc]                       */
+#define PF_JITTER_MAXB 8192      /* pf_jitter_fit sorts a parameter's column in LDS: 12 bytes per theta-particle (96 KiB)          */
+
+/* `JitterKernel.fit` + `robust_var` (jittering.py:51-89, 141-225) and the clamp of `JitterKernel.jitter` (jittering.py:131) for the
+ * unconstrained stacked parameters values (B, P) and the theta log-weights logw (B), B <= PF_JITTER_MAXB, one workgroup per
+ * parameter: the weights as pyfilter.utils.normalize defines them (as in pf_theta_fit), their ESS, the weighted mean and variance,
+ * the robust variance min(IQR / 1.349, sigma)^2 - the quartiles being the values at the FIRST index minimising |cdf - 0.25| and
+ * |cdf - 0.75| of the weights accumulated along the (stably) sorted column, the variance replaced where iqr^2 <= var -, the family's
+ * bandwidth factor (bw clamped to [bw_lo, bw_hi]: the reference's EPS, 1 - EPS).  fit (4, P) DOUBLES <- mean, scale, std =
+ * max(scale, min_std), ESS: what pf_jitter_apply reads, kept in double so that a jittered value is rounded once.  mean / scale_out
+ * (P values of `dtype`, or NULL): the first two rows in the caller's type.  scale (P values of `dtype`, or NULL): PF_JITTER_CONSTANT's
+ * per-parameter scale instead of par. */
+int pf_jitter_fit(const void* values, const void* logw, int64_t B, int32_t P, int32_t kind, double par, const void* scale,
+                  double min_std, double bw_lo, double bw_hi, int dtype, double* fit, void* mean, void* scale_out, void* stream);
+
+/* `JitterKernel.jitter` / `_jitter` (jittering.py:14-26, 119-133) and the rest of `OnlineKernel.update` (online.py:29-45) per
+ * theta-particle i with ancestor ancestors[i]: u = location + std * eps with the family's location at the ancestor (see the kinds);
+ * discrete != 0: u = (1 - s) x[anc] + s u with s ~ Bernoulli(B^-1/2) (online.py:38-45).  u_out (B, P) <- u; x_out[p] (B) <- the
+ * constrained value of parameter p (its prior's bijection, as pf_theta_propose writes it: `context.unstack_parameters`).  `values`
+ * are the parameters BEFORE the resampling - the gather by ancestor happens here.  eps (B, P) / select (B; 0 or 1) of `dtype`: the
+ * draws of a parity run; NULL: Philox keyed by (seed, counter = the update's number, particle, parameter). */
+int pf_jitter_apply(const pf_theta_priors* priors, const void* values, const int64_t* ancestors, const double* fit, int64_t B,
+                    int32_t kind, double par, double bw_lo, double bw_hi, int32_t discrete, const void* eps, const void* select,
+                    uint64_t seed, uint64_t counter, int dtype, void* u_out, void* const* x_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------ *
  * fused filter loop: BaseFilter.batch_filter / filter (filters/base.py:140-221) for SISR (sisr.py:14-56) and
  * APF (apf.py:16-46) with Bootstrap / LinearGaussianObservations on a built-in model; one kernel per step.

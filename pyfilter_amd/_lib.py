@@ -32,11 +32,13 @@ EXPORTS = (
     "pf_filter_graph_destroy", "pf_columns_gather", "pf_columns_exchange", "pf_debug_draw_normals", "pf_debug_launch_trace",
     "pf_smooth_fixed_lag", "pf_smooth_ffbs", "pf_observed_flags", "pf_theta_ess", "pf_theta_fit", "pf_theta_propose",
     "pf_theta_accept", "pf_theta_path", "pf_theta_resample", "pf_initial_sample_cols", "pf_theta_step", "pf_host_alloc",
-    "pf_host_free", "pf_filter_observe",
+    "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply",
 )
 
 
 THETA_MAXP = 8
+JITTER_NONSHRINKING, JITTER_SHRINKING, JITTER_LIUWEST, JITTER_CONSTANT = 0, 1, 2, 3  # include/pf_amd.h: PF_JITTER_*
+JITTER_MAXB = 8192  # PF_JITTER_MAXB: the theta-particles pf_jitter_fit sorts in LDS
 
 
 class PfThetaPriors(C.Structure):
@@ -144,6 +146,10 @@ def load() -> C.CDLL:
     lib.pf_theta_fit.argtypes = [vp, vp, i64, i32, C.c_double, i32, vp, vp, vp]
     lib.pf_theta_propose.argtypes = [C.POINTER(PfThetaPriors), vp, vp, vp, i64, i32, vp, C.POINTER(vp), vp, vp]
     lib.pf_theta_accept.argtypes = [vp] * 11 + [i64, i32, i32, vp, vp, vp, vp]
+    dbl = C.c_double
+    lib.pf_jitter_fit.argtypes = [vp, vp, i64, i32, i32, dbl, vp, dbl, dbl, dbl, i32, vp, vp, vp, vp]
+    lib.pf_jitter_apply.argtypes = [C.POINTER(PfThetaPriors), vp, vp, vp, i64, i32, dbl, dbl, dbl, i32, vp, vp, u64, u64, i32, vp,
+                                    C.POINTER(vp), vp]
     lib.pf_debug_draw_normals.argtypes = [u64, u32, i64, vp, i64, i64, i64, i32, vp]
     lib.pf_debug_launch_trace.argtypes = [C.POINTER(C.c_int32), i32]
     for name in EXPORTS:

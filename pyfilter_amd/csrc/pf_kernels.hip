@@ -2230,6 +2230,67 @@ extern "C" int pf_theta_resample(const void* logw, int64_t B, double u, int dtyp
     });
 }
 
+// ---- NESS: the jittering kernels (pf_jitter.hpp) ---------------------------------------------------------------------------
+#include "pf_jitter.hpp"
+static inline bool jitter_kind_ok(int kind, double par) {
+    if (kind < PF_JITTER_NONSHRINKING || kind > PF_JITTER_CONSTANT) return false;
+    return kind != PF_JITTER_LIUWEST || (par >= 0.0 && par <= 1.0);
+}
+
+extern "C" int pf_jitter_fit(const void* values, const void* logw, int64_t B, int32_t P, int32_t kind, double par, const void* scale,
+                             double min_std, double bw_lo, double bw_hi, int dtype, double* fit, void* mean, void* scale_out,
+                             void* stream) {
+    if (!values || !logw || !fit || B < 1 || B > PF_JITTER_MAXB || P < 1 || P > PF_THETA_MAXP || !jitter_kind_ok(kind, par))
+        return PF_EINVAL;
+    int n2 = 1;
+    while (n2 < (int)B) n2 <<= 1;
+    const size_t lds = kind == PF_JITTER_CONSTANT ? 0 : (size_t)n2 * (sizeof(double) + sizeof(int));
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        auto kernel = k_jitter_fit<T>;
+        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            return (int)PF_EINVAL;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)P), dim3(PF_BLOCK), lds, st, (const T*)values, (const T*)logw, (int)B, (int)P, n2,
+                           (int)kind, par, (const T*)scale, min_std, bw_lo, bw_hi, fit, (T*)mean, (T*)scale_out);
+        return launch_status();
+    });
+}
+
+extern "C" int pf_jitter_apply(const pf_theta_priors* priors, const void* values, const int64_t* ancestors, const double* fit, int64_t B,
+                               int32_t kind, double par, double bw_lo, double bw_hi, int32_t discrete, const void* eps,
+                               const void* select, uint64_t seed, uint64_t counter, int dtype, void* u_out, void* const* x_out,
+                               void* stream) {
+    if (!priors || !values || !ancestors || !fit || !u_out || !x_out || B < 1 || B > 0x7fffffff || priors->P < 1 ||
+        priors->P > PF_THETA_MAXP || !jitter_kind_ok(kind, par))
+        return PF_EINVAL;
+    ThetaPriors pr;
+    ThetaOut out;
+    pr.P = priors->P;
+    for (int p = 0; p < PF_THETA_MAXP; ++p) {
+        pr.kind[p] = p < pr.P ? priors->kind[p] : 0;
+        pr.a[p] = p < pr.P ? priors->a[p] : 0.0;
+        pr.b[p] = p < pr.P ? priors->b[p] : 1.0;
+        out.x[p] = p < pr.P ? x_out[p] : nullptr;
+        if (p < pr.P && (!x_out[p] || pr.kind[p] < 0 || pr.kind[p] > PF_PRIOR_UNIFORM)) return PF_EINVAL;
+    }
+    JitterDraws dr;
+    dr.eps = eps;
+    dr.select = select;
+    dr.seed = (unsigned long long)seed;
+    dr.counter = (unsigned long long)counter;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((B + PF_BLOCK - 1) / PF_BLOCK));
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_jitter_apply<T>), grid, dim3(PF_BLOCK), 0, st, pr, (const T*)values, ancestors, fit, (int)B, (int)kind, par,
+                           bw_lo, bw_hi, (int)discrete, 1.0 / sqrt((double)B), dr, (T*)u_out, out);
+        return launch_status();
+    });
+}
+
 extern "C" int pf_theta_ess(const void* logw, int64_t rows, int64_t B, int dtype, void* out, void* stream) {
     if (!logw || !out || B < 1 || rows < 0 || rows > 0x7fffffff) return PF_EINVAL;
     if (rows == 0) return PF_OK;

@@ -32,7 +32,7 @@ class RunHints:
         self.fused_step = True       # ``filter()`` of a built-in model takes the fused single-step move
         self.fused_batch = True      # ``batch_filter()`` of a built-in model takes the fused run
         self.graph = True            # repeated fused runs of one configuration replay a captured hipGraph
-        self.theta_kernels = True    # SMC^2 / PMMH moves of scalar standard-family priors: theta arithmetic in pf_theta_* (else torch)
+        self.theta_kernels = True    # SMC^2 / PMMH moves and NESS updates of scalar standard-family priors: theta arithmetic in pf_theta_* / pf_jitter_* (else torch)
         self.direct = False          # every plain fused run takes the direct driver (no persistent plan, no graph), not only single-launch runs
 
     def key(self):

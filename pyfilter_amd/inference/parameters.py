@@ -196,6 +196,11 @@ class ThetaParticles:
         self._cache = {"u": u}
         self._keep_prior(prior_u)
 
+    def adopt_jittered(self, u: torch.Tensor):
+        """The value tensors were just written by ``ops.jitter_apply`` from the unconstrained ``u (B, P)`` (a NESS update): ``u``
+        is what is known about them - the log prior of the old values is not."""
+        self._cache = {"u": u}
+
     def _keep_prior(self, prior_u: torch.Tensor):
         row = self._prior_row()
         if row is not None and prior_u.data_ptr() != row.data_ptr():

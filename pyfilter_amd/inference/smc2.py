@@ -354,6 +354,65 @@ class ParticleMetropolisHastings:
         return res
 
 
+def online_move(alg, y: torch.Tensor, state: SMC2State):
+    """The filters' move for one observation and ``w += ll_t`` (``sequential/state.py:35-44``) for an observation-by-observation
+    loop - ``SMC2.step`` and ``NESS.step`` share it.  Returns the new (ESS, every weight finite) pair as host numbers; ``alg``
+    carries the filter and keeps the host slot."""
+    # the reference's host branch (smc2.py:59-62) needs (ESS, all finite) on the host after every observation: the kernel
+    # that updates the theta-weights writes the pair into host memory as well, and the host polls for it - no copy command
+    slot = alg.__dict__.get("_host_slot")
+    if slot is None and state.w.is_cuda:
+        try:
+            slot = alg._host_slot = _ops.HostSlot()
+        except _ops.L.PfAmdError as e:  # (no coherent host memory to be had: the copy command per observation it is)
+            import warnings
+
+            warnings.warn(f"SMC2.step: no host slot ({e}); the statistics travel by a copy command per observation")
+            slot = alg._host_slot = False
+    slot = slot or None
+    # With the slot this loop reads something the device wrote after EVERY move - so the move may take the column-cluster
+    # kernel, whose launches report instead of hanging when they cannot make progress (hints.py): the move's status word
+    # rides through pf_theta_step into the slot, and a move that gave up is issued again on the per-step route.
+    filt = alg.filter
+    # The fast driver (filters/particle/base.py: _OnlineRun): the loop's moves as pieces of ONE run on one argument block - per
+    # observation one pf_filter_run call, one pf_theta_step call and the poll; the FilterResult catches up when somebody looks
+    # (state.filter_state: the rejuvenation below, the caller).  Same kernels, same draws per seed as the path below.
+    if slot is not None and state._theta_step_applies() and hasattr(filt, "online_run"):
+        run = state._online
+        if (run is None or run.filt is not filt or run.result is not state._filter_state) and \
+                state.__dict__.get("_online_na") is not state._filter_state:
+            run = state._online = filt.online_run(state._filter_state)
+            if run is None:
+                state._online_na = state._filter_state  # (asked once per result: the path below it is)
+        if run is not None and isinstance(y, torch.Tensor) and y.numel() == run.o:  # (one observation row shared by the filters)
+            ess, finite = run.observe(y, state.w, slot)
+            stats, row = run.last_stats
+            state.stats = stats[row]
+            state.ess.append(state.stats[0])
+            return ess, finite
+    watching = slot is not None and state._theta_step_applies() and hasattr(filt, "_online_cluster")
+    if watching:
+        filt._online_cluster = True
+    try:
+        filter_state = filt.filter(y, state.filter_state.latest_state, result=state.filter_state)
+    finally:
+        if watching:
+            filt._online_cluster = False
+    watched = getattr(filt, "_watched_move", None) if watching else None
+    if watched is None:
+        ess, finite = slot.wait() if state.append(filter_state, slot) else state.stats.tolist()
+    else:
+        total = state.filter_state._loglikelihood
+        state.append(filter_state, slot, acc=total, status=watched[0])
+        ess, finite = slot.wait()
+        if slot.status:  # the launch gave up: nothing was added - the move again, on the per-step route, and its update
+            watched[1]()
+            state.ess.pop()
+            state.append(filter_state, slot, acc=total)
+            ess, finite = slot.wait()
+    return ess, finite
+
+
 class SMC2:
     """``SMC2(filter_, particles, threshold, kernel)`` (``smc2.py:11-65``).  ``filter_`` is built with a model *builder*
     ``theta -> StateSpaceModel`` (the reference's ``context -> model``); ``priors`` maps parameter names to distributions.
@@ -405,60 +464,7 @@ class SMC2:
     def _step(self, y: torch.Tensor, state: SMC2State) -> SMC2State:
         """One observation (``smc2.py:53-65``)."""
         state.append_data(y)
-        # the reference's host branch (smc2.py:59-62) needs (ESS, all finite) on the host after every observation: the kernel
-        # that updates the theta-weights writes the pair into host memory as well, and the host polls for it - no copy command
-        slot = self.__dict__.get("_host_slot")
-        if slot is None and state.w.is_cuda:
-            try:
-                slot = self._host_slot = _ops.HostSlot()
-            except _ops.L.PfAmdError as e:  # (no coherent host memory to be had: the copy command per observation it is)
-                import warnings
-
-                warnings.warn(f"SMC2.step: no host slot ({e}); the statistics travel by a copy command per observation")
-                slot = self._host_slot = False
-        slot = slot or None
-        # With the slot this loop reads something the device wrote after EVERY move - so the move may take the column-cluster
-        # kernel, whose launches report instead of hanging when they cannot make progress (hints.py): the move's status word
-        # rides through pf_theta_step into the slot, and a move that gave up is issued again on the per-step route.
-        filt = self.filter
-        # The fast driver (filters/particle/base.py: _OnlineRun): the loop's moves as pieces of ONE run on one argument block - per
-        # observation one pf_filter_run call, one pf_theta_step call and the poll; the FilterResult catches up when somebody looks
-        # (state.filter_state: the rejuvenation below, the caller).  Same kernels, same draws per seed as the path below.
-        if slot is not None and state._theta_step_applies() and hasattr(filt, "online_run"):
-            run = state._online
-            if (run is None or run.filt is not filt or run.result is not state._filter_state) and \
-                    state.__dict__.get("_online_na") is not state._filter_state:
-                run = state._online = filt.online_run(state._filter_state)
-                if run is None:
-                    state._online_na = state._filter_state  # (asked once per result: the path below it is)
-            if run is not None and isinstance(y, torch.Tensor) and y.numel() == run.o:  # (one observation row shared by the filters)
-                ess, finite = run.observe(y, state.w, slot)
-                stats, row = run.last_stats
-                state.stats = stats[row]
-                state.ess.append(state.stats[0])
-                if ess < self._threshold * self.particles[0] or not finite:
-                    state = self._kernel.update(self.theta, self.filter, state, generator=self._gen)
-                return state
-        watching = slot is not None and state._theta_step_applies() and hasattr(filt, "_online_cluster")
-        if watching:
-            filt._online_cluster = True
-        try:
-            filter_state = filt.filter(y, state.filter_state.latest_state, result=state.filter_state)
-        finally:
-            if watching:
-                filt._online_cluster = False
-        watched = getattr(filt, "_watched_move", None) if watching else None
-        if watched is None:
-            ess, finite = slot.wait() if state.append(filter_state, slot) else state.stats.tolist()
-        else:
-            total = state.filter_state._loglikelihood
-            state.append(filter_state, slot, acc=total, status=watched[0])
-            ess, finite = slot.wait()
-            if slot.status:  # the launch gave up: nothing was added - the move again, on the per-step route, and its update
-                watched[1]()
-                state.ess.pop()
-                state.append(filter_state, slot, acc=total)
-                ess, finite = slot.wait()
+        ess, finite = online_move(self, y, state)
         if ess < self._threshold * self.particles[0] or not finite:
             state = self._kernel.update(self.theta, self.filter, state, generator=self._gen)
         return state

@@ -598,6 +598,55 @@ def theta_accept(u_cur, u_star, fwd, rev, prior_cur, prior_star, ll_cur, ll_star
     return log_acc[:b], accepted, log_acc[b]
 
 
+def jitter_fit(values: torch.Tensor, log_w: torch.Tensor, kind: int, par: float = 0.0, scale: Optional[torch.Tensor] = None,
+               min_std: float = 0.0, bw_clamp=(0.0, 1.0)):
+    """The jittering kernel of a NESS update fitted to ``values (B, P)`` (unconstrained) under the log-weights ``log_w (B,)``:
+    ``(fit (4, P) float64: mean, scale, clamped std, ESS; mean (P,), scale (P,) in the values' type)`` - one launch
+    (pf_jitter_fit; ``kernels/jittering.py:51-89, 141-225``).  ``kind``: ``_lib.JITTER_*``; ``par``: Liu-West's ``a`` / the
+    constant kernel's scale (``scale``: one value per parameter instead)."""
+    L.require_gpu(values, log_w)
+    values, log_w = values.contiguous(), log_w.contiguous()
+    b, p = values.shape
+    assert log_w.shape == (b,) and log_w.dtype == values.dtype and log_w.device == values.device and b <= L.JITTER_MAXB
+    if scale is not None:
+        scale = scale.to(device=values.device, dtype=values.dtype).expand(p).contiguous()
+    fit = torch.empty((4, p), dtype=torch.float64, device=values.device)
+    out = torch.empty((2, p), dtype=values.dtype, device=values.device)
+    L.check(L.load().pf_jitter_fit(values.data_ptr(), log_w.data_ptr(), b, p, int(kind), float(par), L.ptr(scale), float(min_std),
+                                   float(bw_clamp[0]), float(bw_clamp[1]), L.dtype_code(values.dtype), fit.data_ptr(), out[0].data_ptr(),
+                                   out[1].data_ptr(), L.stream_ptr()), "pf_jitter_fit")
+    return fit, out[0], out[1]
+
+
+def jitter_apply(priors, values: torch.Tensor, ancestors: torch.Tensor, fit: torch.Tensor, kind: int, par: float, x_out,
+                 discrete: bool = False, eps: Optional[torch.Tensor] = None, select: Optional[torch.Tensor] = None, seed: int = 0,
+                 counter: int = 0, bw_clamp=(0.0, 1.0)) -> torch.Tensor:
+    """Every theta-particle moved to its ancestor's location plus ``std * eps`` -> the jittered unconstrained values ``(B, P)``;
+    the constrained ones are written into the ``P`` tensors ``x_out`` (pf_jitter_apply; ``jittering.py:14-26, 119-133``,
+    ``online.py:29-45``).  ``eps (B, P)`` / ``select (B,)``: the draws of a parity run - else Philox keyed by ``(seed, counter)``."""
+    L.require_gpu(values, ancestors, fit)
+    values = values.contiguous()
+    b, p = values.shape
+    dt, dev = values.dtype, values.device
+    assert p == priors.P == len(x_out) and fit.shape == (4, p) and fit.dtype == torch.float64 and fit.is_contiguous()
+    assert ancestors.shape == (b,) and ancestors.dtype == torch.int64 and ancestors.is_contiguous()
+    for x in x_out:
+        assert x.is_contiguous() and x.numel() == b and x.dtype == dt and x.device == dev
+    if eps is not None:
+        eps = eps.contiguous()
+        assert eps.shape == (b, p) and eps.dtype == dt and eps.device == dev
+    if select is not None:
+        select = select.contiguous()
+        assert select.shape == (b,) and select.dtype == dt and select.device == dev
+    ptrs = (C.c_void_p * p)(*[x.data_ptr() for x in x_out])
+    u = torch.empty_like(values)
+    L.check(L.load().pf_jitter_apply(C.byref(priors), values.data_ptr(), ancestors.data_ptr(), fit.data_ptr(), b, int(kind), float(par),
+                                     float(bw_clamp[0]), float(bw_clamp[1]), int(bool(discrete)), L.ptr(eps), L.ptr(select),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, L.dtype_code(dt), u.data_ptr(),
+                                     ptrs, L.stream_ptr()), "pf_jitter_apply")
+    return u
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # smoothing over a recorded state history
 # ----------------------------------------------------------------------------------------------------------------
