@@ -131,6 +131,10 @@ template <typename T> struct FusedArgs {
         return (q - 2 >= t0) ? means[((int64_t)(q - 2) * g.B + b) * D + d] : (T)piv0[(int64_t)b * PF_MAXD + d];
     }
     int debug_cut;  // development knob (env PF_DEBUG_CUT): kernels return early after stage n; 0 = off
+    int keep_state;  // per launch: the state this step writes is read by somebody other than the next launch - a recorded state
+                     // (state history) or the last state of a pf_filter_run call - so all its planes are stored.  0: an interior
+                     // state, whose ancestors (APF) and - before an observed APF step, which resamples on the tile partials and the
+                     // scans alone - log-weights would be overwritten unread: those stores are skipped (step_body, stage 4)
 };
 
 // `late`: an opaque zero added to the row addresses (the step kernel ties it to a value computed after the ancestor
@@ -223,9 +227,12 @@ template <typename T, int D, bool WQ = true> struct PartialAcc {
     // doubles, `redm` >= 2 * PF_NWAVES Ts, neither used by anything still in flight.  The within-wave sums run in T (for
     // float: 6 DPP adds per quantity instead of fp64 pairs of moves), everything above a wave is fp64.  WITH_ES: the
     // Exp(1) spacings of the multinomial route are reduced too.  F1 / F2: this thread's factors exp(m - M).
-    template <bool WITH_ES>
+    // `before(f1, f2)` runs once the factors are known, ahead of the second exchange's barrier (its own LDS words ride in that
+    // exchange); `after()` right behind the barrier, ahead of the record fold (single-round tiles: the tile scan and the store of
+    // the next scans - step_body)
+    template <bool WITH_ES, typename FB, typename FA>
     __device__ __forceinline__ void finish(double* part, int b, int k, int B, int tiles, bool pre_on, double* red, T* redm,
-                                           int32_t* poison_slot, T& M1_out, T& M2_out, T& F1_out, T& F2_out) {
+                                           int32_t* poison_slot, T& M1_out, T& M2_out, T& F1_out, T& F2_out, FB&& before, FA&& after) {
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
         const T w1 = wave_max<T>(m1), w2 = wave_max<T>(m2);
         if (lane == 0) {
@@ -265,7 +272,9 @@ template <typename T, int D, bool WQ = true> struct PartialAcc {
             if (lane == 0) red[NS * PF_NWAVES + wid] = ws;
         }
         if (poison) atomicOr(poison_slot, 1);
+        before(f1, f2);
         __syncthreads();
+        after();
         // the tile's record: lane q of wave 0 adds the four waves' sums of quantity q (same order as a single thread would:
         // identical values) and stores it to its row - one pass of ~10 instructions instead of thread 0 walking NS + 1
         // quantities and 6 + 2 D stores one after the other at the very end of the workgroup's critical path
@@ -535,7 +544,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_fused_reduce(FusedArgs<T> a) {
         chunk_scan_round<T, VEC>(rw, on, l_col + r0, threadIdx.x * VEC, r * PF_NWAVES + (threadIdx.x >> 6), use_lds ? crec : nullptr, ct_tile);
     }
     T M1, M2, F1, F2;
-    acc.template finish<true>(a.part_w(a.step), b, k, g.B, g.tiles, false, red, redm, &a.poison[(a.step & 3) * g.B + b], M1, M2, F1, F2);
+    acc.template finish<true>(a.part_w(a.step), b, k, g.B, g.tiles, false, red, redm, &a.poison[(a.step & 3) * g.B + b], M1, M2, F1, F2, [](T, T) {}, []() {});
     double Mc, Sc;
     finalize_chunk_table<T>(ct_tile, use_lds ? crec : nullptr, rk * PF_NWAVES, reds, redm, Mc, Sc);
     if (threadIdx.x == 0) {  // the resampling family's (max, sum) come from the scan
@@ -1428,10 +1437,6 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
         using KArgs = const __attribute__((address_space(4))) FusedArgs<T>;
         KArgs* la = (KArgs*)((const_ptr<char>)__builtin_amdgcn_kernarg_segment_ptr() + late);
         T* const x_out = la->x[slot ^ 1];
-#ifndef PF_DEVTOOLS
-        T* const lw_out = la->logw[slot ^ 1] + (int64_t)b * g.N;
-        int32_t* const anc_col = la->anc + (int64_t)b * g.N;
-#endif
         if constexpr (FAST) {
             // scalar loads of the run's record (k_fused_reduce wrote it) and of this / the next step's observation
             const_ptr<T> yq = (const_ptr<T>)(uintptr_t)a.y + late;
@@ -1526,24 +1531,42 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
                 if (j & 1) __builtin_amdgcn_sched_barrier(0);
             }
             PF_STAMP(a, 12);
+            // Planes of an interior state that nobody reads are not stored (FusedArgs::keep_state; uniform): an APF names new
+            // ancestors at every move, and the APF step after an observed one always resamples (apf.py:29-31) - from the tile
+            // partials and the scans, never from the incoming log-weights (lw_in is read under !resample only).  A following
+            // unobserved step carries the weights and reads them, SISR keeps ancestors across its non-resampling steps: both
+            // keep every store.  A plane that is not stored has its destination pointer not fetched either (flag and pointers
+            // are fetched here, where they are used: they hold no SGPRs through the arithmetic above).
+            const bool keep = la->keep_state != 0;
+            const bool st_anc = keep || !apf;
+            const bool st_lw = keep || !(apf && obs && pre_next);
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 T* xc = x_out + ((int64_t)d * g.B + b) * g.N + r0;  // (the round's first particle: uniform)
                 if (VEC == 1) xc[tid] = xo[d][0]; else store_out<T, VEC, !MULTI>(xc, tid * VEC, xo[d]);
             }
-            if (VEC == 1) lw_out[i0] = lwo[0]; else store_out<T, VEC, !MULTI>(lw_out + r0, tid * VEC, lwo);
+            if (st_lw) {
+                T* const lw_st = la->logw[slot ^ 1] + (int64_t)b * g.N;
+                if (VEC == 1) lw_st[i0] = lwo[0]; else store_out<T, VEC, !MULTI>(lw_st + r0, tid * VEC, lwo);
+            }
             if (resample || apf) {  // SISR without resampling keeps the previous ancestors (sisr.py:25-26)
-                if (VEC == 1) anc_col[i0] = idx[0]; else store_out<int, VEC, !MULTI>(anc_col + r0, tid * VEC, idx);
+                if (st_anc) {
+                    int32_t* const anc_st = la->anc + (int64_t)b * g.N;
+                    if (VEC == 1) anc_st[i0] = idx[0]; else store_out<int, VEC, !MULTI>(anc_st + r0, tid * VEC, idx);
+                }
             } else if (la->anc_prev) {  // ... which, with a state history, means copying them into this state's slot
                 const int32_t* ap = la->anc_prev + (int64_t)b * g.N + i0;
+                int32_t* const anc_st = la->anc + (int64_t)b * g.N;
                 int prev[VEC];
                 if (VEC == 1) prev[0] = ap[0]; else load_vec<int, VEC>(ap, prev);
-                if (VEC == 1) anc_col[i0] = prev[0]; else store_vec<int, VEC>(anc_col + i0, prev);
+                if (VEC == 1) anc_st[i0] = prev[0]; else store_vec<int, VEC>(anc_st + i0, prev);
             }
+#ifdef PF_DEVTOOLS
             if (PF_CUT(a, 5)) {
                 if (pre_next) { if (VEC == 1) lw_out[i0] = pre_n[0]; else store_vec<T, VEC>(lw_out + i0, pre_n); }
                 continue;
             }
+#endif
             T piv[D];  // pivot of the moments of state step + 1: the mean of state step - 1, or the run's record (FusedArgs::pivot)
 #pragma unroll
             for (int d = 0; d < D; ++d)
@@ -1578,27 +1601,64 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     if (PF_CUT(a, 3)) return;
     PF_STAMP(a, 14);
     T M1, M2, F1, F2;
-    acc.template finish<MODE == 1>(a.part_w(step + 1), b, k, g.B, g.tiles, single && pre_next, red, redm, &a.poison[((step + 1) & 3) * g.B + b], M1, M2, F1, F2);
-    if (PF_CUT(a, 6)) return;
-    if (scan_next && single) {
-        // exp(rw - thread max) and the thread's factor exp(thread max - tile max) are in registers (push_round / finish)
-        const int64_t i0 = base + tid * VEC;
-        const bool on = i0 < g.N;
+    // Single-round tiles: the tile scan rides in finish()'s second exchange.  exp(rw - thread max) and the thread's factor
+    // exp(thread max - tile max) are in registers (push_round / finish), the wave totals travel with the wave sums (one barrier
+    // pair instead of two), and the next scans are stored before lane q of wave 0 folds and stores the tile record - the
+    // write-through drain of the plane overlaps the fold.  Same operations on the same operands in the same order as
+    // block_scan_excl.
+    // (The multinomial kernels and the scalar-access ones - VEC = 1: columns whose length is no multiple of four - keep the scan
+    // behind finish(): the former sit at their register limit, where the longer live ranges of the fused form cost scratch, the
+    // latter lose a wave of occupancy to six more VGPRs.)
+    constexpr bool fused_tail = single && MODE != 1 && VEC == 4;
+    const bool tile_scan = scan_next && fused_tail;  // (uniform)
+    const int64_t i0s = base + tid * VEC;
+    const bool on_s = i0s < g.N;
+    double e[VEC], local = 0.0, incl = 0.0;
+    acc.template finish<MODE == 1>(a.part_w(step + 1), b, k, g.B, g.tiles, single && pre_next, red, redm, &a.poison[((step + 1) & 3) * g.B + b], M1, M2, F1, F2,
+        [&](T f1, T f2) {
+            if (!tile_scan) return;
+            const T f = pre_next ? f2 : f1;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                local += on_s ? (double)(e_rw[j] * f) : 0.0;
+                e[j] = local;
+            }
+            incl = wave_scan_incl(local, tid & 63);
+            if ((tid & 63) == 63) reds[tid >> 6] = incl;
+        },
+        [&]() {
+            if (!tile_scan) return;
+            double wave_off = 0.0;
+#pragma unroll
+            for (int w = 0; w < PF_NWAVES; ++w) {
+                const double sw = reds[w];
+                if (w < (tid >> 6)) wave_off += sw;
+            }
+            const double excl = wave_off + incl - local;
+            if (on_s) {
+                T outv[VEC];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) outv[j] = (T)(excl + e[j]);
+                if (VEC == 1) l_next[i0s] = outv[0]; else store_out<T, VEC, !MULTI>(l_next + base, tid * VEC, outv);
+            }
+        });
+    if (PF_CUT(a, 6)) return;  // (development: with the fused tail the scan has already run - cut 6 then ends behind it)
+    if (scan_next && single && !fused_tail) {
         const T f = pre_next ? F2 : F1;
-        double e[VEC], local = 0.0, total;
+        double total;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            local += on ? (double)(e_rw[j] * f) : 0.0;
+            local += on_s ? (double)(e_rw[j] * f) : 0.0;
             e[j] = local;
         }
         const double excl = block_scan_excl(local, reds, total);
-        if (on) {
+        if (on_s) {
             T outv[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) outv[j] = (T)(excl + e[j]);
-            if (VEC == 1) l_next[i0] = outv[0]; else store_out<T, VEC, !MULTI>(l_next + base, tid * VEC, outv);
+            if (VEC == 1) l_next[i0s] = outv[0]; else store_out<T, VEC, !MULTI>(l_next + base, tid * VEC, outv);
         }
-    } else if (scan_next) {
+    } else if (scan_next && !single) {
         // the chunk table of the next step's resampling weights, and the tile's (max, sum) of that family from the same sums
         double Mc, Sc;
         finalize_chunk_table<T>(ct_tile, use_lds ? sh.crec : nullptr, rk * PF_NWAVES, reds, redm, Mc, Sc);

@@ -2441,6 +2441,7 @@ static FusedArgs<T> make_fused_args(const pf_filter_args* A, const Geom& g, cons
     a.finalize_only = 0;
     a.t0 = (int)t0;
     a.debug_cut = 0;
+    a.keep_state = 1;  // (the per-step route sets it per launch: filter_run_impl)
 #ifdef PF_DEVTOOLS  // (the instrumented build of tools/pmc_stages.py: stage cuts / cycle stamps selected per process)
     if (const char* dc = getenv("PF_DEBUG_CUT")) a.debug_cut = atoi(dc);
 #endif
@@ -2716,7 +2717,12 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
         place(t);
         a.obs = flags.obs(t);
         a.obs_next = (s + 1 < n_steps) ? flags.obs(t + 1) : (prepare_next ? 1 : 0);
+        // Which states are read by somebody other than the next launch: every recorded one (state history) and the last of this
+        // call - the caller's latest state, the next piece's k_fused_reduce, an online move - whatever finalize, resume or
+        // prepare_next say.  The step kernel skips the stores of an interior state's planes that would be overwritten unread.
+        a.keep_state = (ring != 0 || s + 1 == n_steps) ? 1 : 0;
 #ifdef PF_DEVTOOLS
+        if (a.debug_cut != 0) a.keep_state = 1;  // (the stage cuts 2 / 4 / 5 write through lw_out / anc_col)
         // stage cuts on ONE launch (the last but one step) when PF_DEBUG_CUT_AT_END is set: the state entering it is
         // valid, so per-dispatch PMC rows of that launch profile the stages on real data
         static const bool cut_at_end = getenv("PF_DEBUG_CUT_AT_END") != nullptr;
