@@ -293,7 +293,7 @@ template <typename T, int VEC> __device__ __forceinline__ void store_vec(T* __re
 // read again by the launch that writes them).  Plain stores leave these lines dirty in the write-back L2 until the
 // end-of-kernel release writes them back, and the next launch waits for that (MI355X_MICROARCH.md "boundary": + B / 6 TB/s
 // behind B dirty bytes - 16.8 MB per step at 2^20 particles).  `sc1` stores write through to the memory side while the
-// workgroup is still computing: measured (profiles/r03_out_store.txt, tools/out_store_variants.sh) 16.3 -> 14.9 us per step
+// workgroup is still computing: measured (profiles/r03_out_store.txt, tools/out_store_variants.py) 16.3 -> 14.9 us per step
 // at 2^20 x 1, 37.5 -> 36.9 at 2^22 x 1, 39.5 -> 38.3 at 64 x 65 536; non-temporal stores (policy 1) gain the same at
 // 2^20 but lose 4-9 % at the larger shapes; `sc0 sc1` equals `sc1`.  PF_OUT_STORE: 0 plain, 1 non-temporal, 2 write-through.
 // Policy 2 goes through a buffer descriptor - `buffer_store_dwordx4 ... offen sc1` from

@@ -6,378 +6,12 @@
 // needs inter-workgroup communication inside a launch (the kernel boundary is the only synchronisation).
 //
 // HBM-bound by design: no MFMA anywhere - there is no dense contraction on this path.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <vector>
-
-#include <type_traits>
-
-#include "../../include/pf_amd.h"
-#include "pf_device.hpp"
-#include "pf_models.hpp"
-#include "pf_philox.hpp"
-#include "pf_linear.hpp"
+// This is the main unit (pf_main.o): the stand-alone primitives and every extern "C" entry.  The fused runs' kernels are compiled in
+// the other units (pf_step.hip, pf_column.hip, pf_cluster.hip); filter_run_checked, at the end of this file, checks a run's arguments
+// and hands it to the route that takes it.
+#include "pf_host.hpp"
 
 namespace pf {
-
-// ---------------------------------------------------------------------------------------------------------------
-// geometry
-// ---------------------------------------------------------------------------------------------------------------
-#define PF_MAX_TILES 1024
-#define PF_TARGET_WGS 1024
-#define PF_AUTO_FLAGS 128  // steps whose observed flags pf_filter_run derives itself (workspace slot)
-
-struct Geom {
-    int64_t N;
-    int B;
-    int vec;            // 4 when N % 4 == 0 else 1
-    int round_elems;    // 256 * vec
-    int rounds_per_tile;
-    int tile_elems;
-    int tiles;          // per column
-};
-
-// `target`: workgroups per launch the tile size aims at (pf_run_hints.tile_target; 0 = PF_TARGET_WGS)
-static inline Geom make_geom(int64_t N, int64_t B, int64_t target = 0) {
-    Geom g;
-    g.N = N;
-    g.B = (int)B;
-    g.vec = (N % 4 == 0) ? 4 : 1;
-    g.round_elems = PF_BLOCK * g.vec;
-    const int64_t rounds_total = (N + g.round_elems - 1) / g.round_elems;
-    // Tile size: every workgroup pays a fixed price (column combine, constants, reductions), so tiles grow until the
-    // grid is down to ~PF_TARGET_WGS workgroups (4 per CU) - but never more than PF_MAX_TILES tiles per column.
-    int min_r = (g.vec == 4) ? 1 : 4;  // >= 1024-particle tiles
-    if (target <= 0) target = PF_TARGET_WGS;
-    int64_t r = (rounds_total * B) / target;
-    if (r > rounds_total) r = rounds_total;
-    const int64_t r_cap = (rounds_total + PF_MAX_TILES - 1) / PF_MAX_TILES;
-    if (r < r_cap) r = r_cap;
-    if (r < min_r) r = min_r;
-    g.rounds_per_tile = (int)r;
-    g.tile_elems = g.rounds_per_tile * g.round_elems;
-    g.tiles = (int)((N + g.tile_elems - 1) / g.tile_elems);
-    return g;
-}
-
-// per-column bookkeeping that survives between steps (lives in the workspace)
-struct ColStat {
-    double lse_w;      // log sum exp of the current log-weights
-    double base_lse;   // ll_t = lse(logw'_t) - base_lse   (see DESIGN.md "log-likelihood bookkeeping")
-    int resample;      // this step resamples this column
-    int prev_observed; // the previous step was a weighted (observed) step
-    int ll_done;       // the previous step's log-likelihood was already flushed by a finalize-only pass
-    int pad;
-};
-
-// workspace carve-up (all offsets 256-byte aligned)
-struct WsLayout {
-    size_t off_part;   // double partials[2][(6 + 2 PF_MAXD)][B][tiles]
-    size_t part_elems;
-    size_t off_stat;   // ColStat[B]
-    size_t off_poison; // int32 [4][B]
-    size_t off_ctr;    // int32 [4] (reserved) | at +64: uint8 [PF_AUTO_FLAGS] observed flags derived on the device
-    size_t off_dbg;    // uint64 [32]: development timestamps (clock64) of workgroup (0, 0)
-    size_t off_cpack;  // T [B][PK_N] (sized for double): the run's closed-form records
-    size_t off_piv0;   // double [B][PF_MAXD]: the run's moment pivots
-    size_t off_ctab;   // double [2][B][tiles * rounds_per_tile * 4][2]: per-chunk (offset, factor) of the chunk-local scans
-    size_t ctab_elems;
-    size_t off_clu;    // cluster route (pf_cluster.hpp; columns of PF_CLUSTER_MIN_N < N <= PF_CLUSTER_MAX_N particles): int32 error
-                       // word (256 B) | granule records [2][B][PF_CLUSTER_NG][64] x 16 B; absent (clu_bytes = 0) otherwise
-    size_t clu_bytes;
-    size_t off_tree;   // T [B][cdf_tree_total(N)]: the cdf sampled at every 16th, 256th, ... entry (the stand-alone multinomial's search tables)
-    size_t total;
-};
-
-// pf_multinomial's search tables (the "cdf tree"): level l holds the LAST cdf entry of every block of 16^(l+1) entries (the column's last
-// entry, 1, closes every level); levels are padded to 16 entries, the top one has at most 16.  N <= 2^30: at most 7 levels, N / 15
-// entries in all.  Sizes and offsets are recomputed where they are used (a handful of scalar shifts): kept in per-thread arrays indexed
-// by a run-time level they were promoted to LDS / scratch - 18 KB of LDS in k_scan.
-__host__ __device__ static inline int cdf_tree_levels(int64_t N) {
-    int levels = 0;
-    int64_t n = N;
-    do {
-        n = (n + 15) >> 4;
-        ++levels;
-    } while (n > 16 && levels < 8);
-    return levels;
-}
-__host__ __device__ static inline void cdf_tree_level(int64_t N, int l, int& size, int& off) {
-    int64_t n = (N + 15) >> 4;
-    int o = 0;
-    for (int i = 0; i < l; ++i) {
-        o += (int)((n + 15) & ~(int64_t)15);
-        n = (n + 15) >> 4;
-    }
-    size = (int)n;
-    off = o;
-}
-__host__ __device__ static inline int cdf_tree_total(int64_t N) {  // entries per column
-    int size, off;
-    cdf_tree_level(N, cdf_tree_levels(N) - 1, size, off);
-    return off + ((size + 15) & ~15);
-}
-
-// the cluster route's column sizes: above what one workgroup holds (pf_column.hpp), at most 64 chunks of 256 particles
-#define PF_CLUSTER_MIN_N 2048
-#define PF_CLUSTER_MAX_N 16384
-#define PF_CLUSTER_NG 8  // granules per chunk record, the largest instantiation (double, D = 3: 24 words)
-
-static inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
-static inline WsLayout make_ws(const Geom& g) {  // (partials sized for PF_MAXD states)
-    WsLayout w;
-    size_t o = 0;
-    w.off_part = o;  // two copies (the fused pipeline double-buffers them by state parity)
-    w.part_elems = (size_t)(6 + 2 * PF_MAXD) * g.B * g.tiles;
-    o = align256(o + 2 * sizeof(double) * w.part_elems);
-    w.off_stat = o;
-    o = align256(o + sizeof(ColStat) * (size_t)g.B);
-    w.off_poison = o;
-    o = align256(o + sizeof(int32_t) * 4 * (size_t)g.B);
-    w.off_ctr = o;
-    o = align256(o + 64 + PF_AUTO_FLAGS);
-    w.off_dbg = o;
-    o = align256(o + 256);
-    w.off_cpack = o;
-    o = align256(o + sizeof(double) * (size_t)g.B * 24);
-    w.off_piv0 = o;
-    o = align256(o + sizeof(double) * (size_t)g.B * PF_MAXD);
-    w.off_ctab = o;
-    w.ctab_elems = (size_t)g.B * g.tiles * g.rounds_per_tile * PF_NWAVES * 2;
-    o = align256(o + 2 * sizeof(double) * w.ctab_elems);
-    w.off_clu = o;
-    // (16 KB per column - reserved only for batches the route can take in a handful of launches: <= 8 192 member workgroups)
-    w.clu_bytes = (g.N > PF_CLUSTER_MIN_N && g.N <= PF_CLUSTER_MAX_N && g.N % 4 == 0 && ((g.N + 1023) / 1024) * (int64_t)g.B <= 8192)
-                      ? 256 + (size_t)2 * g.B * PF_CLUSTER_NG * 64 * 16 : 0;
-    o = align256(o + w.clu_bytes);
-    w.off_tree = o;  // pf_multinomial: 16-ary search tables over the cdf (cdf_tree_*), sized for double
-    o = align256(o + sizeof(double) * (size_t)g.B * cdf_tree_total(g.N));
-    w.total = o;
-    return w;
-}
-
-// Upper bound of make_ws(...).total over every tile geometry make_geom can produce for (N, B) (any `target`): the partials
-// are largest with the most tiles per column (the smallest tiles), the chunk table never holds more than
-// rounds_total + one tile's rounds per column.
-static inline size_t ws_bound(int64_t N, int64_t B) {
-    Geom g = make_geom(N, B, (int64_t)1 << 40);  // a huge target = the smallest tiles = the most tiles per column
-    const int64_t rounds_total = (N + g.round_elems - 1) / g.round_elems;
-    const size_t most_tiles = make_ws(g).total;
-    g.tiles = 1;
-    g.rounds_per_tile = (int)(2 * rounds_total + 2);  // tiles * rounds_per_tile <= rounds_total + rounds_per_tile <= 2 rounds_total
-    const size_t most_chunks = make_ws(g).total;
-    return most_tiles + most_chunks;
-}
-
-// partial slots
-// E: sum of the tile's Exp(1) spacings (sorted-uniform multinomial); MX[d] at 6+d, MXX[d] at 6+D+d
-enum { PQ_M1 = 0, PQ_S1 = 1, PQ_Q1 = 2, PQ_M2 = 3, PQ_S2 = 4, PQ_E = 5, PQ_MX = 6 };
-
-// ---------------------------------------------------------------------------------------------------------------
-// wave-cooperative lower_bound over a non-decreasing array: first j in [0, n) with c[j] >= p (clamped to n-1).
-// 64-ary search: each round the 64 lanes probe 64 equally spaced elements and a ballot picks the sub-range.
-// ---------------------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ int wave_lower_bound(const T* __restrict__ c, int n, T p, int lane) {
-    int lo = 0, hi = n;
-    while (hi - lo > PF_WAVE) {
-        const int len = hi - lo;
-        const int step = (len + PF_WAVE - 1) / PF_WAVE;
-        int probe = lo + (lane + 1) * step - 1;
-        if (probe > hi - 1) probe = hi - 1;
-        const bool ge = c[probe] >= p;
-        const unsigned long long bal = __ballot(ge);
-        if (bal == 0ull) return n - 1;  // p above every element (or NaNs): clamp
-        const int f = __ffsll((long long)bal) - 1;
-        int nhi = lo + (f + 1) * step;
-        if (nhi > hi) nhi = hi;
-        lo = lo + f * step;
-        hi = nhi;
-    }
-    const int idx = lo + lane;
-    const bool ge = (idx < hi) ? (c[idx] >= p) : true;
-    const unsigned long long bal = __ballot(ge);
-    const int f = __ffsll((long long)bal) - 1;
-    int r = lo + f;
-    return r > n - 1 ? n - 1 : r;
-}
-
-// plain per-thread lower_bound on global memory in [lo, hi)
-template <typename T> __device__ __forceinline__ int thread_lower_bound(const T* __restrict__ c, int lo, int hi, T p) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (c[mid] < p) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// searchsorted position of the systematic grid: (i + u) / N evaluated exactly as resampling.py:44-46 does in T
-template <typename T> __device__ __forceinline__ T grid_position(int64_t i, T u, T n_as_t) { return (T(i) + u) / n_as_t; }
-
-// ---------------------------------------------------------------------------------------------------------------
-// The systematic grid inverted: K(c) = #{ i in [0, N) : grid_position(i) <= c }.  With it the ancestor of position i is
-// the entry j with K(cdf_{j-1}) <= i < K(cdf_j) - the same relation searchsorted(side=left) defines - and no search
-// is needed: every cdf entry computes its own offspring range in closed form (branch-free, so weight degeneracy does
-// not make lanes diverge).  Exactness: the candidate floor(c N - u) + 1 is at most one off the true K (both the fma
-// and the rounding of grid_position move the decision for at most one i while N * eps <= 1/4, i.e. N <= 2^22 in
-// float, any N in double), so evaluating the grid position - with exactly the arithmetic of grid_position - at the two
-// neighbouring indices settles it.  Larger float grids walk from the candidate to the exact boundary (step kernel).
-// POW2: N is a power of two - the division is an exact multiplication by `rcN` = 1 / N.
-// ---------------------------------------------------------------------------------------------------------------
-template <typename T, bool POW2> __device__ __forceinline__ T grid_value(T x_plus_u, T nT, T rcN) {
-    return POW2 ? x_plus_u * rcN : x_plus_u / nT;
-}
-template <typename T, bool POW2> __device__ __forceinline__ int grid_count(T c, T u, T nT, T rcN, int N) {
-    T t = __builtin_fma(c, nT, -u);
-    t = __builtin_fmin(__builtin_fmax(t, T(-1)), nT);  // +inf (beyond the column) -> N; NaN -> -1
-    const T fl = __builtin_floor(t);
-    const T pa = grid_value<T, POW2>(fl + u, nT, rcN), pb = grid_value<T, POW2>((fl + T(1)) + u, nT, rcN);
-    const int K = (int)fl + ((pa <= c) ? 1 : 0) + ((pb <= c) ? 1 : 0);
-    return K < 0 ? 0 : (K > N ? N : K);
-}
-// offspring counts relative to the round's first position r0, clamped to the round: [0, RE]
-template <typename T, int VEC, bool POW2>
-__device__ __forceinline__ void grid_counts_local(const T (&c)[VEC], T u, T nT, T rcN, int N, int r0, int RE,
-                                                  int (&out)[VEC]) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        const int k = grid_count<T, POW2>(c[j], u, nT, rcN, N) - r0;
-        out[j] = k < 0 ? 0 : (k > RE ? RE : k);
-    }
-}
-
-// One round of 256 * VEC consecutive systematic grid positions [r0, r0 + RE) against the 2 * 256 * VEC cdf entries
-// starting at ws that the threads hold in registers (c0: entries ws + tid * VEC + j, c1: the same + 256 * VEC; +inf
-// beyond the column).  Every entry computes how many of the round's positions lie at or below it (grid_count); entry q
-// owns positions [K_{q-1}, K_q) and writes q + 1 at the head of that range in `hd`; a running maximum over the round's
-// positions spreads the heads.  No search, no divergence.  `hd` (RE + 64 ints) must have its first RE entries zeroed before
-// the call (the first barrier inside orders that against the scatter); `fallback(i, from)` resolves positions the
-// window does not reach (from = first index not staged, or 0 when - defensively - no head precedes the position).
-// sh_cl: 2 * PF_NWAVES ints, sh_wm: PF_NWAVES ints.  Three barriers.
-#define PF_MAX_WINDOWS 12
-// `next_window(it, d0, d1)` stages the cdf entries [ws + it * S, ws + (it + 1) * S) the same way (returns false when
-// the column ends before them).  It is only called when the windows so far do not account for all RE positions - a
-// stretch of negligible weights - and lets the workgroup walk on window by window (up to PF_MAX_WINDOWS) before the
-// remaining positions fall back to per-position binary searches, whose ~20 dependent loads would set the duration of
-// the whole kernel.
-// V1: entries per thread of the window's second part.  A window is S = 256 * (VEC + V1) entries: thread t holds entries
-// t * VEC + j (c0) and 256 * VEC + t * V1 + j (c1).  V1 = VEC is the 2 x 256 x VEC window of the stand-alone resampler;
-// the fused step kernel uses V1 = 1 - 256 * VEC positions rarely need more than 256 * (VEC + 1) entries when the window
-// starts within tile / 64 of the first ancestor, and every entry staged is an entry read, mapped and counted.
-template <typename T, int VEC, int V1, typename NextWindow, typename Fallback>
-__device__ __forceinline__ void inverse_grid_round(const T (&c0)[VEC], const T (&c1)[V1], int ws, int r0i, int RE, int N,
-                                                   T ub, T nT, T rcN, bool pow2, int64_t i0, int* hd, int* sh_cl, int* sh_wm,
-                                                   NextWindow&& next_window, Fallback&& fallback, int (&idx)[VEC]) {
-    constexpr int S = PF_BLOCK * (VEC + V1);
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wid = tid >> 6;
-    const int dump = RE + lane;
-    // counts of one staged window -> heads; returns the number of positions accounted for so far
-    auto scatter_window = [&](const T (&w0)[VEC], const T (&w1)[V1], int qbase, int covered_before) -> int {
-        int cn0[VEC], cn1[V1];
-        if (pow2) {
-            grid_counts_local<T, VEC, true>(w0, ub, nT, rcN, N, r0i, RE, cn0);
-            grid_counts_local<T, V1, true>(w1, ub, nT, rcN, N, r0i, RE, cn1);
-        } else {
-            grid_counts_local<T, VEC, false>(w0, ub, nT, rcN, N, r0i, RE, cn0);
-            grid_counts_local<T, V1, false>(w1, ub, nT, rcN, N, r0i, RE, cn1);
-        }
-        if (lane == 63) {
-            sh_cl[wid] = cn0[VEC - 1];
-            sh_cl[PF_NWAVES + wid] = cn1[V1 - 1];
-        }
-        __syncthreads();  // the wave-boundary counts are visible; `hd` is zeroed
-        int pv0 = wave_prev(cn0[VEC - 1], 0), pv1 = wave_prev(cn1[V1 - 1], 0);
-        if (lane == 0) {
-            pv0 = wid ? sh_cl[wid - 1] : covered_before;  // entries before the first window own no position of this round
-            pv1 = sh_cl[PF_NWAVES + wid - 1];              // wave 0: the first part's last entry
-        }
-        const int covered = sh_cl[2 * PF_NWAVES - 1];
-        // branch-free scatter: entries without offspring in this round write to a per-lane dump slot behind the RE heads
-        // (exec-mask juggling per conditional store costs ~5 scalar instructions, a v_cndmask one vector instruction)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const int lo0 = j ? cn0[j - 1] : pv0;
-            hd[(cn0[j] > lo0) ? lo0 : dump] = qbase + tid * VEC + j + 1;
-        }
-#pragma unroll
-        for (int j = 0; j < V1; ++j) {
-            const int lo1 = j ? cn1[j - 1] : pv1;
-            hd[(cn1[j] > lo1) ? lo1 : dump] = qbase + PF_BLOCK * VEC + tid * V1 + j + 1;
-        }
-        return covered;
-    };
-    int covered = scatter_window(c0, c1, 0, 0);  // positions of this round the window(s) account for
-    int windows = 1;
-    for (; windows < PF_MAX_WINDOWS && covered < RE; ++windows) {  // uniform: `covered` comes from LDS
-        __syncthreads();                                            // everyone has read sh_cl
-        T d0[VEC], d1[V1];
-        if (!next_window(windows, d0, d1)) break;
-        covered = scatter_window(d0, d1, windows * S, covered);
-    }
-    __syncthreads();
-    int h[VEC];
-    if (VEC == 1) h[0] = hd[tid]; else load_vec<int, VEC>(hd + tid * VEC, h);
-#pragma unroll
-    for (int j = 1; j < VEC; ++j) h[j] = imax(h[j], h[j - 1]);
-    const int inc = wave_scan_max(h[VEC - 1]);
-    if (lane == 63) sh_wm[wid] = inc;
-    __syncthreads();
-    int carry = wave_prev(inc, 0);
-#pragma unroll
-    for (int w = 0; w < PF_NWAVES - 1; ++w) carry = (w < wid) ? imax(carry, sh_wm[w]) : carry;
-    const int64_t beyond = (int64_t)ws + (int64_t)windows * S;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        const int64_t i = i0 + j;
-        const int q = imax(carry, h[j]);
-        int res = ws + q - 1;
-        if (i < N && (tid * VEC + j >= covered || q == 0)) res = fallback(i, (q == 0) ? 0 : (int)(beyond < N ? beyond : N));
-        idx[j] = (i < N && res < N) ? res : N - 1;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Window search shared by the stand-alone resampler and the fused step kernel.
-// For one round of 256*VEC consecutive grid positions: stage cdf[j0, j0 + WIN) in LDS, every thread lower_bounds its
-// VEC positions inside the window (falling back to a global binary search beyond it), and the ancestor of the
-// round's last position becomes the next round's window start (ancestors are non-decreasing).
-// ---------------------------------------------------------------------------------------------------------------
-template <typename T, int VEC> struct SearchWin {
-    static constexpr int WIN = 2 * PF_BLOCK * VEC;
-};
-
-// Branch-free lower_bound of VEC values in the LDS window (WIN a power of two): log2(WIN) + 1 rounds of "probe, compare,
-// advance" with all VEC probes of a round in flight together.  The same instruction stream for every lane - no
-// exec-mask juggling (the galloping search above spends as many scalar as vector instructions on divergent loops).
-// Returns positions in [0, WIN] (WIN = beyond the window).
-template <typename T, int WIN, int VEC>
-__device__ __forceinline__ void window_lower_bound_flat(const T* win, const T (&p)[VEC], int (&out)[VEC]) {
-    static_assert((WIN & (WIN - 1)) == 0, "window size must be a power of two");
-    // positions as BYTE offsets: a probe is one ds_read with an immediate offset, a round compare + select + add per position
-    // (element indices cost a shift and an add more per probe: 21 against 16 VALU per round of four positions)
-    const unsigned char* const wb = reinterpret_cast<const unsigned char*>(win);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) out[j] = 0;
-#pragma unroll
-    for (int step = WIN / 2; step >= 1; step >>= 1) {
-        T v[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[j] = *reinterpret_cast<const T*>(wb + out[j] + (step - 1) * (int)sizeof(T));
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) out[j] += (v[j] < p[j]) ? step * (int)sizeof(T) : 0;
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-        out[j] += (*reinterpret_cast<const T*>(wb + out[j]) < p[j]) ? (int)sizeof(T) : 0;
-        out[j] /= (int)sizeof(T);
-    }
-}
 
 template <typename T, int VEC>
 __device__ __forceinline__ void systematic_round(const T* __restrict__ cdf_col, int N, int64_t i0, T u,
@@ -1654,121 +1288,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_ffbs(ModelDesc md, const T* __rest
 
 }  // namespace pf
 
-#include "pf_fused.hpp"
-#include "pf_column.hpp"
-#include "pf_cluster.hpp"
-
-namespace pf {
-// pf_filter_observe -> the route that carries the run: what the theta update needs (the cluster route folds it into its launch and
-// says so; every other route leaves it to a pf_theta_step launch)
-struct ThetaFold {
-    void* w;
-    const void* ll;
-    void* stats;
-    void* slot;
-    uint64_t seq;
-    void* acc;
-    int folded;
-};
-}  // namespace pf
-
 // =================================================================================================================
 // C ABI
 // =================================================================================================================
-using namespace pf;
-
-// PF_OK, or the error of the launches since the last check (hipGetLastError)
-static inline int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PF_OK : (int)e;
-}
-#define PF_CHECK_LAUNCH()                          \
-    do {                                           \
-        if (const int e_ = launch_status()) return e_; \
-    } while (0)
-
-// Run-time values as compile-time constants: each with_* calls the generic lambda `f` with a tag of the value and returns its result
-template <int V> using int_c = std::integral_constant<int, V>;
-// the C ABI's element type: f(float{}) or f(double{}); PF_EINVAL (nothing called) for any other dtype
-template <typename F> static inline int with_dtype(int dtype, F&& f) {
-    if (dtype == PF_F32) return f(float{});
-    if (dtype == PF_F64) return f(double{});
-    return PF_EINVAL;
-}
-// particles per lane of a tile geometry (Geom::vec): 4, else 1
-template <typename F> static inline int with_vec(int vec, F&& f) { return vec == 4 ? f(int_c<4>{}) : f(int_c<1>{}); }
-// the state dimension of the built-in models: 1, 2, else 3 (check_model bounds it)
-template <typename F> static inline int with_d3(int64_t D, F&& f) {
-    return D == 1 ? f(int_c<1>{}) : D == 2 ? f(int_c<2>{}) : f(int_c<3>{});
-}
-// ... of PF_HID_LINEAR_MAT: 1 .. 8 (PF_LIN_MAXD), PF_EUNSUPPORTED otherwise
-template <typename F> static inline int with_d8(int64_t D, F&& f) {
-    switch (D) {
-        case 1: return f(int_c<1>{}); case 2: return f(int_c<2>{}); case 3: return f(int_c<3>{}); case 4: return f(int_c<4>{});
-        case 5: return f(int_c<5>{}); case 6: return f(int_c<6>{}); case 7: return f(int_c<7>{}); case 8: return f(int_c<8>{});
-        default: return PF_EUNSUPPORTED;
-    }
-}
-template <typename F> static inline int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-
-static inline bool bad_shape(int64_t N, int64_t B) { return N < 1 || B < 1 || N > (int64_t)1 << 30 || B > 65535; }
-
-// `fused`: the call is a fused filter run - the only place a user-defined affine process (whose mean / scale planes
-// travel in pf_filter_args) can be evaluated; the stand-alone model kernels take built-in kinds only
-static inline int check_model(const pf_model* m, bool fused = false) {
-    if (!m || !m->params) return PF_EINVAL;
-    if (m->hid_kind == PF_HID_USER_AFFINE && !fused) return PF_EUNSUPPORTED;
-    if (m->hid_kind == PF_HID_LINEAR_MAT) {  // the stand-alone model kernels only (pf_linear.hpp): no fused / column route
-        if (fused || m->dim < 1 || m->dim > PF_LIN_MAXD || m->obs_dim < 1 || m->obs_dim > PF_LIN_MAXO || m->obs_kind != PF_OBS_LINEAR)
-            return PF_EUNSUPPORTED;
-        return PF_OK;
-    }
-    if (m->dim < 1 || m->dim > PF_MAXD || m->obs_dim < 1 || m->obs_dim > PF_MAXO) return PF_EUNSUPPORTED;
-    if (m->dim == 1 && m->obs_dim != 1) return PF_EUNSUPPORTED;
-    if (m->hid_kind < 0 || m->hid_kind > PF_HID_USER_AFFINE) return PF_EUNSUPPORTED;
-    if (m->hid_kind == PF_HID_LORENZ63_EM && m->dim != 3) return PF_EUNSUPPORTED;
-    if (m->obs_kind != PF_OBS_LINEAR && m->obs_kind != PF_OBS_SV) return PF_EUNSUPPORTED;
-    if (m->obs_kind == PF_OBS_SV && m->dim != 1) return PF_EUNSUPPORTED;
-    return PF_OK;
-}
-
-static inline ModelDesc to_desc(const pf_model* m) {
-    ModelDesc d;
-    d.hid_kind = m->hid_kind;
-    d.obs_kind = m->obs_kind;
-    d.obs_dim = m->obs_dim;
-    d.dt = m->dt;
-    d.inc_scale = m->inc_scale;
-    return d;
-}
-
-// The fused-run instantiation matrix compiles as several translation units (the build runs them in parallel):
-//   -DPF_TU_NO_F64 -DPF_TU_NO_F32DN -DPF_TU_NO_F32D1 : the main unit - C ABI and the stand-alone primitives
-//   -DPF_TU_F32D1_ONLY -DPF_TU_VEC=4|1 : only the float32 fused kernels of scalar states for one vector width
-//   -DPF_TU_F32DN_ONLY              : only the float32 fused kernels of D > 1 states
-//   -DPF_TU_F64_ONLY                : only the float64 fused kernels
-//   ... each of the kernel units additionally with -DPF_TU_MULTI=0|1: only the kernels of single-round / multi-round
-//   tiles (the MULTI template argument of k_fused_step) - with their entries, the filter_run_impl instantiations (see below)
-// Without any of the macros the file is a single self-contained unit.
-#if defined(PF_TU_COLUMN_F32) || defined(PF_TU_COLUMN_F64) || defined(PF_TU_CLUSTER_F32) || defined(PF_TU_CLUSTER_F64)
-// the column-persistent / column-cluster kernels of one arithmetic type, nothing else
-#define PF_TU_NO_API
-#define PF_TU_NO_F64
-#define PF_TU_NO_F32DN
-#define PF_TU_NO_F32D1
-#endif
-#if defined(PF_TU_NO_F64) || defined(PF_TU_NO_F32DN) || defined(PF_TU_NO_F32D1) || defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
-#define PF_TU_SPLIT  // a split build: the column kernels live in their own units (PF_TU_COLUMN_F32 / _F64)
-#endif
-#if !defined(PF_TU_SPLIT) || defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
-#define PF_TU_STEP  // the unit compiles k_fused_step kernels: filter_run_impl's definition and the instantiations it owns
-#endif
-#if defined(PF_TU_F64_ONLY) || defined(PF_TU_F32DN_ONLY) || defined(PF_TU_F32D1_ONLY)
-#define PF_TU_NO_API
-#endif
-#ifndef PF_TU_NO_API
 #ifndef PF_SOURCE_SHA256
-#define PF_SOURCE_SHA256 "unknown"
+#error "pf_kernels.hip: -DPF_SOURCE_SHA256='\"<digest>\"' is required (__graft_entry__.unit_command passes the tree's source_digest())"
 #endif
 #define PF_STR2(x) #x
 #define PF_STR(x) PF_STR2(x)
@@ -2357,27 +1881,6 @@ extern "C" int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_st
     });
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// fused loop
-// ---------------------------------------------------------------------------------------------------------------
-#endif  // !PF_TU_NO_API
-
-// Test support: which step-kernel instantiation each launch of the calling thread's most recent fused runs selected
-// (pf_debug_launch_trace).  A per-thread ring, written on the host at launch time - nothing a kernel ever reads.
-#define PF_TRACE_LEN 2048
-#define PF_TRACE_FIELDS 10
-struct LaunchTrace {
-    int32_t rec[PF_TRACE_LEN][PF_TRACE_FIELDS];
-    uint64_t count;
-};
-LaunchTrace& launch_trace();
-static inline void trace_launch(int step, int tbytes, int d, int vec, int mode, int prop, int fast, int spec, int mk, int multi) {
-    LaunchTrace& t = launch_trace();
-    int32_t* r = t.rec[t.count % PF_TRACE_LEN];
-    r[0] = step; r[1] = tbytes; r[2] = d; r[3] = vec; r[4] = mode; r[5] = prop; r[6] = fast; r[7] = spec; r[8] = mk; r[9] = multi;
-    ++t.count;
-}
-#ifndef PF_TU_NO_API
 LaunchTrace& launch_trace() {
     static thread_local LaunchTrace t = {};
     return t;
@@ -2391,649 +1894,7 @@ extern "C" int pf_debug_launch_trace(int32_t* out, int max_records) {
         for (int f = 0; f < PF_TRACE_FIELDS; ++f) out[i * PF_TRACE_FIELDS + f] = t.rec[(t.count - n + i) % PF_TRACE_LEN][f];
     return n;
 }
-#endif
 
-// the launch arguments every fused kernel shares, from the C ABI's argument block
-template <typename T>
-static FusedArgs<T> make_fused_args(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0) {
-    FusedArgs<T> a;
-    a.md = to_desc(&A->model);
-    a.params = (const T*)A->model.params;
-    a.filter = A->filter;
-    a.proposal = A->proposal;
-    a.resampler = A->resampler;
-    a.g = g;
-    a.thr_abs = A->ess_threshold * (double)A->N;
-    a.logN = log((double)A->N);
-    a.rcN = T(1) / T(A->N);
-    a.seed = A->seed;
-    a.seed_dev = (const uint64_t*)A->step_counter;
-    a.x[0] = (T*)A->x[0];
-    a.x[1] = (T*)A->x[1];
-    a.logw[0] = (T*)A->logw[0];
-    a.logw[1] = (T*)A->logw[1];
-    a.anc = A->anc;
-    a.anc_prev = nullptr;
-    a.cdf = (T*)A->cdf;
-    a.pos = (T*)A->pos;
-    a.y = (const T*)A->y;
-    a.y_rows = (int)A->y_rows;
-    a.z_tape = (const T*)A->z_tape;
-    a.u_tape = (const T*)A->u_tape;
-    a.user_loc = (const T*)A->user_loc;
-    a.user_scale = (const T*)A->user_scale;
-    a.user_scale_percol = A->user_scale_per_column != 0 ? 1 : 0;
-    a.user_dt = (T)A->user_dt;
-    a.means = (T*)A->means;
-    a.vars = (T*)A->vars;
-    a.ll_steps = (T*)A->ll_steps;
-    a.ll_total = (T*)A->ll_total;
-    a.part = (double*)((char*)A->ws + wl.off_part);
-    a.part_stride = (int64_t)wl.part_elems;
-    a.stat = (ColStat*)((char*)A->ws + wl.off_stat);
-    a.poison = (int32_t*)((char*)A->ws + wl.off_poison);
-    a.dbg = (unsigned long long*)((char*)A->ws + wl.off_dbg);
-    a.cpack = (T*)((char*)A->ws + wl.off_cpack);
-    a.piv0 = (double*)((char*)A->ws + wl.off_piv0);
-    a.ctab = (double*)((char*)A->ws + wl.off_ctab);
-    a.ctab_stride = (int64_t)wl.ctab_elems;
-    static_assert(PK_N == 24, "workspace layout reserves 24 slots per column record");
-    a.finalize_only = 0;
-    a.t0 = (int)t0;
-    a.debug_cut = 0;
-    a.keep_state = 1;  // (the per-step route sets it per launch: filter_run_impl)
-#ifdef PF_DEVTOOLS  // (the instrumented build of tools/pmc_stages.py: stage cuts / cycle stamps selected per process)
-    if (const char* dc = getenv("PF_DEBUG_CUT")) a.debug_cut = atoi(dc);
-#endif
-    return a;
-}
-
-// A run's observed flags: the caller's host array (A->observed), the caller's device array (A->observed_dev), or - neither given -
-// derived from y on the device into the workspace slot at off_ctr + 64 (runs of <= PF_AUTO_FLAGS steps); a run of ONE step on a
-// shared observation row (the online move) has its kernels look at the row itself instead: no launch derives a flag byte
-template <typename T>
-struct ObsFlags {
-    const uint8_t* host;  // A->observed
-    const uint8_t* dev;   // the flags the kernels read on the device, indexed by the absolute step (null: host or inline)
-    bool inline_y;        // the kernels read the flag off y (FusedArgs::obs = -2, ColumnRun::inline_y)
-    bool derive;          // dev is the workspace slot: a launch of the route derives it (launch_derive / launch_zero)
-    uint8_t* slot;
-    int64_t row;          // elements of y per step
-    const T* y;           // (derive) the run's first observation row
-
-    ObsFlags(const pf_filter_args* A, const WsLayout& wl, int64_t t0, int64_t n_steps) {
-        const bool none = !A->observed && !A->observed_dev && n_steps > 0;
-        host = A->observed;
-        inline_y = none && n_steps == 1 && A->y_rows == 1;
-        derive = none && !inline_y;
-        slot = (uint8_t*)A->ws + wl.off_ctr + 64;
-        row = A->y_rows * (int64_t)A->model.obs_dim;
-        y = derive ? (const T*)A->y + t0 * row : nullptr;
-        dev = derive ? slot - t0 : A->observed_dev;
-    }
-    // FusedArgs::obs of step t
-    int obs(int64_t t) const { return inline_y ? -2 : dev ? -1 : (host[t] != 0); }
-    // the derivation in a launch of its own: one wave per step
-    void launch_derive(int64_t n_steps, hipStream_t st) const {
-        hipLaunchKernelGGL((k_observed_flags<T>), dim3((unsigned)n_steps), dim3(PF_WAVE), 0, st, y, row, slot);
-    }
-    // clears `words` words at p - with `flags`, the derivation rides along: one launch (a kernel, not hipMemsetAsync: captured as a
-    // memset node the fill stopped clearing these records after ~195 replays of the same executable graph on ROCm 7.2 - every
-    // log-likelihood of the run came back NaN, "poisoned" - tools/graph_replays.py)
-    void launch_zero(uint32_t* p, size_t words, bool flags, int64_t n_steps, hipStream_t st) const {
-        const unsigned zb = (unsigned)((words + PF_BLOCK - 1) / PF_BLOCK);
-        if (flags)
-            hipLaunchKernelGGL((k_zero_and_flags<T>), dim3(zb + (unsigned)n_steps), dim3(PF_BLOCK), 0, st, p, words, zb, y, row, slot);
-        else
-            hipLaunchKernelGGL((k_zero_words<uint32_t>), dim3(zb), dim3(PF_BLOCK), 0, st, p, words);
-    }
-    // a persistent launch's piece (pf_column.hpp, pf_cluster.hpp): up to 32 * PFC_OBS_WORDS steps from the absolute step t
-    ColumnRun piece(int64_t t, int64_t left) const {
-        ColumnRun r;
-        r.t0 = (int)t;
-        r.n_steps = (int)(left < 32 * PFC_OBS_WORDS ? left : 32 * PFC_OBS_WORDS);
-        r.use_bits = (dev == nullptr && !inline_y) ? 1 : 0;
-        r.inline_y = inline_y ? 1 : 0;
-        for (int w = 0; w < PFC_OBS_WORDS; ++w) r.obs_bits[w] = 0u;
-        if (r.use_bits)
-            for (int q = 0; q < r.n_steps; ++q)
-                if (host[r.t0 + q]) r.obs_bits[q >> 5] |= 1u << (q & 31);
-        return r;
-    }
-};
-
-// pf_filter_run_timed: HIP events on the caller's stream around a route's timed window (none without kernel_ms), released on every path
-struct KernelTimer {
-    float* kernel_ms;
-    hipStream_t st;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool failed = false;  // hipEventCreate failed: the route returns rc
-    int rc = PF_OK;
-    KernelTimer(float* kernel_ms_, hipStream_t st_) : kernel_ms(kernel_ms_), st(st_) {
-        if (!kernel_ms) return;
-        for (auto& e : ev)
-            if (hipEventCreate(&e) != hipSuccess) {
-                failed = true;
-                rc = (int)hipGetLastError();
-                return;
-            }
-        (void)hipEventRecord(ev[0], st);
-    }
-    ~KernelTimer() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void stop() const {
-        if (kernel_ms) (void)hipEventRecord(ev[1], st);
-    }
-    // waits for the stream: kernel_ms[0] = kernel_ms[2] = the window per time step, kernel_ms[1] = 0 (the planning kernel of
-    // earlier versions: folded into the step kernel's prologue)
-    int finish(int64_t n_steps) const {
-        if (!kernel_ms) return PF_OK;
-        const hipError_t se = hipStreamSynchronize(st);
-        if (se != hipSuccess) return (int)se;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-        kernel_ms[0] = kernel_ms[2] = n_steps > 0 ? ms / (float)n_steps : 0.f;
-        kernel_ms[1] = 0.f;
-        return PF_OK;
-    }
-};
-
-// The persistent routes' folded instantiations (pf_column.hpp / pf_cluster.hpp: KIND / FILT / PROP): a run on Philox normals of one
-// of the model kinds KINDS calls f(kind, filter, proposal) - each a std::integral_constant - and returns true; any other run calls
-// nothing and returns false.  A kind comes with its observations and proposals: the Verhulst process with stochastic-volatility
-// observations and Bootstrap, every other kind with linear observations and Bootstrap or LGO.
-template <int... KINDS, typename F>
-static bool with_folded(const pf_filter_args* A, F&& f) {
-    bool hit = false;
-    auto with_kind = [&](auto kind_c) {
-        constexpr bool SV = decltype(kind_c)::value == PF_HID_VERHULST_EM;
-        if (hit || A->model.hid_kind != decltype(kind_c)::value || A->model.obs_kind != (SV ? PF_OBS_SV : PF_OBS_LINEAR)) return;
-        if (A->proposal != PF_PROP_BOOTSTRAP && (SV || A->proposal != PF_PROP_LGO)) return;
-        hit = true;
-        auto with_prop = [&](auto filt_c) {
-            if constexpr (!SV) {
-                if (A->proposal == PF_PROP_LGO) return f(kind_c, filt_c, int_c<PF_PROP_LGO>{});
-            }
-            f(kind_c, filt_c, int_c<PF_PROP_BOOTSTRAP>{});
-        };
-        if (A->filter == PF_FILTER_APF) with_prop(int_c<PF_FILTER_APF>{});
-        else with_prop(int_c<PF_FILTER_SISR>{});
-    };
-    if (!A->z_tape) (with_kind(int_c<KINDS>{}), ...);
-    return hit;
-}
-
-// Columns of fewer tiles than this keep their books inline (the column's last step workgroup, after its own work).  Since
-// the bookkeepers are dispatched LAST (the grid's slowest axis is the tile index, see below) they cost nothing on the critical path and inline lost at every
-// shape measured, single-tile columns included (1 024 x 8 192: 65.5 -> 59.1 us per step; 256 x 8 192 27.3 -> 22.1;
-// profiles/r04c_step_kernel_book_inline_threshold_ab.txt): 1 = never.  (Round 2's rule was 8.)
-#define PF_BOOK_INLINE_TILES 1
-// The per-step route of one arithmetic type / state dimension / vector width / tile geometry: declared in every unit, defined in the
-// units that compile k_fused_step kernels and instantiated (below) only in the one that owns it - see the translation-unit note above
-template <typename T, int D, int VEC, bool MULTI>
-int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize,
-                    hipStream_t st, float* kernel_ms);
-#ifdef PF_TU_STEP
-template <typename T, int D, int VEC, bool MULTI>
-int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize,
-                    hipStream_t st, float* kernel_ms) {
-    FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
-
-    const dim3 grid_tiles(g.tiles, g.B), block(PF_BLOCK);
-    // the step kernel: one workgroup per tile + one bookkeeper per column, dispatched after all step workgroups
-    // (PF_BOOK_INLINE=0/1 overrides in the development build: 1 = the column's last step workgroup keeps the books)
-    a.book_inline = g.tiles < PF_BOOK_INLINE_TILES ? 1 : 0;
-#ifdef PF_DEVTOOLS
-    if (const char* bi = getenv("PF_BOOK_INLINE")) a.book_inline = atoi(bi);  // (2: nobody keeps the books - timing experiments)
-#endif
-    // Grid (B, tiles + 1), x = the column: blocks are dispatched in linear order and a 2^20-particle step fills every
-    // resident slot of the chip (1 024 = 4 per CU: 33 KB of LDS, 113 VGPRs) - with the tile index slowest the bookkeepers
-    // (y == tiles) come after ALL step workgroups and fill slots as they free up; as block (tiles, b) of a (tiles + 1, B) grid
-    // they sat between the columns, took slots first, and the last columns' step workgroups started 2 - 3 us late
-    // (profiles/r04c_step_kernel_bookkeepers_last_ab.txt).  B = 1 is the same linear order either way.
-    a.kmap = 0u;
-    if (g.B == 1 && g.tiles >= 16 && (g.tiles & (g.tiles - 1)) == 0) {  // one column of 2^q tiles: an eighth of it per XCD
-        unsigned q = 0;
-        while ((1 << q) < g.tiles) ++q;
-        a.kmap = 7u | ((q - 3u) << 8) | (3u << 16);
-    }
-    const dim3 grid(g.B, g.tiles + (a.book_inline ? 0 : 1));
-    const ObsFlags<T> flags(A, wl, t0, n_steps);
-    if (t0 == 0) {
-        // fresh filter: no previous step to account for (column records + poison flags); the derived flags ride along
-        const size_t words = (wl.off_ctr - wl.off_stat) / sizeof(uint32_t);  // (256-byte aligned regions)
-        flags.launch_zero((uint32_t*)((char*)A->ws + wl.off_stat), words, flags.derive, n_steps, st);
-    }
-    // state history: slot pointers per launch (the kernels keep addressing "buffer step & 1 is read, the other written")
-    const int64_t ring = A->ring >= 3 ? A->ring : 0;
-    auto place = [&](int64_t t) {  // launch of step t: reads state t, writes state t + 1
-        if (!ring) return;
-        const int64_t rs = t % ring, wsl = (t + 1) % ring, bn = (int64_t)g.B * g.N;
-        a.x[t & 1] = (T*)A->x[0] + rs * D * bn;
-        a.x[(t + 1) & 1] = (T*)A->x[0] + wsl * D * bn;
-        a.logw[t & 1] = (T*)A->logw[0] + rs * bn;
-        a.logw[(t + 1) & 1] = (T*)A->logw[0] + wsl * bn;
-        a.anc = A->anc + wsl * bn;
-        a.anc_prev = A->anc + rs * bn;
-    };
-    place(t0);
-    // partials of the incoming state (afterwards every step kernel leaves the partials of the state it wrote)
-    a.step = (int)t0;
-    a.obs_dev = flags.dev;
-    if (flags.derive && t0 != 0) flags.launch_derive(n_steps, st);
-    a.obs = n_steps > 0 ? flags.obs(t0) : 0;
-    a.obs_next = 0;
-    // (pf_run_hints.resume: the previous call on this argument block ended with a SISR step that left the partials and local
-    // scans of exactly this state in the workspace - the pass is redundant)
-    // (an APF leaves them when its last step ran with pf_run_hints.prepare_next: the caller's promise)
-    const bool resumed = A->hints.resume != 0 && t0 > 0 && A->ring < 3;
-    const bool prepare_next = A->hints.prepare_next != 0 && A->filter == PF_FILTER_APF && !finalize && n_steps > 0;
-    if (!resumed) hipLaunchKernelGGL((k_fused_reduce<T, D, VEC>), grid_tiles, block, 0, st, a);
-
-    // ancestor stage of the step kernel: 0 inverted grid (systematic), 1 multinomial, 2 systematic by search - float
-    // grids beyond 2^22 positions, where the closed form is not exact (PF_FORCE_SEARCH=1 selects it for testing)
-    const bool force_search = A->hints.ancestor_search != 0;
-    const int mode = (A->resampler == PF_RESAMPLE_MULTINOMIAL)
-                         ? 1
-                         : ((sizeof(T) == 4 && (g.N > ((int64_t)1 << 22) || force_search)) ? 2 : 0);
-    // steady-state specialisation of this launch (float only: the double kernels are the parity path): see SPEC
-    auto spec_of = [&]() -> int {
-        if (sizeof(T) != 4 || a.z_tape || a.obs != 1) return 0;
-        if (a.md.hid_kind == PF_HID_USER_AFFINE && a.filter == PF_FILTER_APF) return 0;  // (its steady state is not instantiated)
-        if (a.filter == PF_FILTER_APF) return a.obs_next == 1 ? 1 : 0;
-        return 2;
-    };
-    auto launch_step_as = [&](auto prop_c, auto fast_c) {
-        constexpr int PROP = decltype(prop_c)::value;
-        constexpr bool FAST = decltype(fast_c)::value;
-        auto go = [&](auto mode_c, auto spec_c) {
-            constexpr int MODE = decltype(mode_c)::value;
-            constexpr int SPEC = decltype(spec_c)::value;
-            auto launch = [&](auto mk_c) {
-                constexpr int MK = decltype(mk_c)::value;
-                trace_launch((int)a.step, (int)sizeof(T), D, VEC, MODE, PROP, FAST ? 1 : 0, SPEC, MK, MULTI ? 1 : 0);
-                hipLaunchKernelGGL((k_fused_step<T, D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI>), grid, block, 0, st, a);
-            };
-            // model kinds folded at compile time for the stochastic-volatility built-in (float runs; for Lorenz-63 the
-            // same specialisation measured no gain)
-            if constexpr (!FAST) {  // user-defined affine process: the parent's (loc, scale) come from the caller's planes
-                if (a.md.hid_kind == PF_HID_USER_AFFINE) {
-                    // (one step per run: no next step, so the APF steady-state specialisation never applies - not instantiated)
-                    if constexpr (SPEC != 1) launch(std::integral_constant<int, 3>{});
-                    return;
-                }
-            }
-            if constexpr (sizeof(T) == 4 && !FAST && D == 1) {
-                if (a.md.hid_kind == PF_HID_VERHULST_EM && a.md.obs_kind == PF_OBS_SV) return launch(std::integral_constant<int, 1>{});
-            }
-            if constexpr (sizeof(T) == 4 && !FAST && D == 3) {  // Lorenz-63
-                if (a.md.hid_kind == PF_HID_LORENZ63_EM && a.md.obs_kind == PF_OBS_LINEAR)
-                    return launch(std::integral_constant<int, 4>{});
-            }
-            if constexpr (sizeof(T) == 4 && FAST && D == 1) {  // shape of the one-step mean of the closed-form models
-                if (a.md.hid_kind == PF_HID_SINE_EM) return launch(std::integral_constant<int, 2>{});
-                return launch(std::integral_constant<int, 1>{});
-            }
-            launch(std::integral_constant<int, 0>{});
-        };
-        auto with_mode = [&](auto mode_c) {
-            if constexpr (sizeof(T) == 4) {
-                const int sp = spec_of();
-                if (sp == 1) return go(mode_c, std::integral_constant<int, 1>{});
-                // (the SISR specialisation spills in the multinomial variant and in the closed-form kernels: measured
-                // slower than the generic kernel there)
-                if (sp == 2) return go(mode_c, std::integral_constant<int, 2>{});
-            }
-            go(mode_c, std::integral_constant<int, 0>{});
-        };
-        if (mode == 0) with_mode(std::integral_constant<int, 0>{});
-        else if (mode == 1) with_mode(std::integral_constant<int, 1>{});
-        else if constexpr (sizeof(T) == 4) go(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
-    };
-    auto launch_step = [&]() {
-        // scalar closed-form models: the proposal is a run-time switch inside one lean kernel (FAST); everything else gets
-        // the proposal as a template constant so that Bootstrap runs do not carry the optimal proposal's registers
-        bool fast = false;
-        if constexpr (D == 1)
-            fast = a.md.obs_kind == PF_OBS_LINEAR && a.md.hid_kind != PF_HID_VERHULST_EM && a.md.hid_kind != PF_HID_USER_AFFINE;
-        if (fast) {
-            if constexpr (D == 1) {
-                if (a.proposal == PF_PROP_BOOTSTRAP) launch_step_as(std::integral_constant<int, PF_PROP_BOOTSTRAP>{}, std::true_type{});
-                else launch_step_as(std::integral_constant<int, PF_PROP_LGO>{}, std::true_type{});
-            }
-        } else if (a.proposal == PF_PROP_BOOTSTRAP) {
-            launch_step_as(std::integral_constant<int, PF_PROP_BOOTSTRAP>{}, std::false_type{});
-        } else {
-            launch_step_as(std::integral_constant<int, PF_PROP_LGO>{}, std::false_type{});
-        }
-    };
-    const KernelTimer timer(kernel_ms, st);  // (around the whole step loop)
-    if (timer.failed) return timer.rc;
-    for (int64_t s = 0; s < n_steps; ++s) {
-        const int64_t t = t0 + s;
-        a.step = (int)t;
-        place(t);
-        a.obs = flags.obs(t);
-        a.obs_next = (s + 1 < n_steps) ? flags.obs(t + 1) : (prepare_next ? 1 : 0);
-        // Which states are read by somebody other than the next launch: every recorded one (state history) and the last of this
-        // call - the caller's latest state, the next piece's k_fused_reduce, an online move - whatever finalize, resume or
-        // prepare_next say.  The step kernel skips the stores of an interior state's planes that would be overwritten unread.
-        a.keep_state = (ring != 0 || s + 1 == n_steps) ? 1 : 0;
-#ifdef PF_DEVTOOLS
-        if (a.debug_cut != 0) a.keep_state = 1;  // (the stage cuts 2 / 4 / 5 write through lw_out / anc_col)
-        // stage cuts on ONE launch (the last but one step) when PF_DEBUG_CUT_AT_END is set: the state entering it is
-        // valid, so per-dispatch PMC rows of that launch profile the stages on real data
-        static const bool cut_at_end = getenv("PF_DEBUG_CUT_AT_END") != nullptr;
-        const int cut_all = a.debug_cut;
-        if (cut_at_end && cut_all > 0 && s != n_steps - 2) a.debug_cut = 0;
-#endif
-        launch_step();
-#ifdef PF_DEVTOOLS
-        a.debug_cut = cut_all;
-#endif
-    }
-    timer.stop();
-    if (finalize) {
-        a.step = (int)(t0 + n_steps);
-        a.obs = a.obs_next = 0;
-        a.finalize_only = 1;
-        hipLaunchKernelGGL((k_fused_book<T, D>), dim3(1, g.B), block, 0, st, a);
-    }
-    // (one kernel per step: the in-sequence time of a step IS the step kernel's launch-to-launch duration)
-    if (const int rc = timer.finish(n_steps)) return rc;
-    return launch_status();
-}
-
-// explicit instantiations: each unit the leaves it owns; the main unit, which dispatches to them (filter_run_checked), sees the
-// declaration alone and compiles no k_fused_step kernel
-#define PF_LEAF_AT(T, D, VEC, MULTI) \
-    template int filter_run_impl<T, D, VEC, MULTI>(const pf_filter_args*, const Geom&, const WsLayout&, int64_t, int64_t, int, hipStream_t, float*);
-#ifdef PF_TU_MULTI
-#define PF_LEAF(T, D, VEC) PF_LEAF_AT(T, D, VEC, PF_TU_MULTI != 0)
-#else
-#define PF_LEAF(T, D, VEC) PF_LEAF_AT(T, D, VEC, false) PF_LEAF_AT(T, D, VEC, true)
-#endif
-#if !defined(PF_TU_NO_F32D1) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32DN_ONLY)
-#if !defined(PF_TU_VEC) || PF_TU_VEC == 4
-PF_LEAF(float, 1, 4)
-#endif
-#if !defined(PF_TU_VEC) || PF_TU_VEC == 1
-PF_LEAF(float, 1, 1)
-#endif
-#endif
-#if !defined(PF_TU_NO_F32DN) && !defined(PF_TU_F64_ONLY) && !defined(PF_TU_F32D1_ONLY)
-PF_LEAF(float, 2, 4) PF_LEAF(float, 3, 4) PF_LEAF(float, 2, 1) PF_LEAF(float, 3, 1)
-#endif
-#if !defined(PF_TU_NO_F64) && !defined(PF_TU_F32DN_ONLY) && !defined(PF_TU_F32D1_ONLY)
-PF_LEAF(double, 1, 4) PF_LEAF(double, 2, 4) PF_LEAF(double, 3, 4) PF_LEAF(double, 1, 1) PF_LEAF(double, 2, 1) PF_LEAF(double, 3, 1)
-#endif
-#undef PF_LEAF
-#undef PF_LEAF_AT
-#endif  // PF_TU_STEP
-
-// ---- the column-persistent route (pf_column.hpp): filters of a few hundred .. a few thousand particles -----------------
-// One launch per run (per PFC_OBS_WORDS * 32 steps): no reduce / bookkeeping launches, no per-column records.
-static inline int column_threads(int64_t N, int vec) {
-    const int64_t need = (N + vec - 1) / vec;
-    return (int)(((need + PF_WAVE - 1) / PF_WAVE) * PF_WAVE);
-}
-// Particles per lane on the column route: four - for scalar states also when N % 4 != 0 (the per-step geometry's
-// one-particle lanes need four times the waves per filter, and past 256 of them the 1024-thread kernel: 1 000 x 333 ran
-// 16.3 us per step against 5.4 for 1 000 x 400): the kernel handles the ragged last lane and the unaligned columns itself
-// (pf_column.hpp: `ragged`).  D > 1 keeps the geometry's width.  The state's layout in HBM and the Philox addressing do not
-// depend on it.  (One particle per lane for ALIGNED columns measured <= 16 % faster below 512 filters x 256 particles and
-// up to 3x slower above: profiles/r03_column_vec1_vs_vec4.txt - not adopted.)
-#define PF_COLUMN_VEC 4
-static inline size_t column_lds_bytes(int64_t N, int D, size_t tsize, int vec) {
-    int64_t np2 = 64;
-    while (np2 < N) np2 <<= 1;
-    const int64_t NP = ((N + vec - 1) / vec) * vec;  // (the kernel's padded plane stride)
-    const size_t planes = (((size_t)(np2 + PF_LB_PAD + (int64_t)D * NP) * tsize) + 15) & ~(size_t)15;  // (cdf + the search's pad | particle planes)
-    return planes + sizeof(double) * (2 + 2 * (4 + 2 * D)) * PFC_MAXW + 16;  // scan records + the state's records (x 2)
-}
-// (measured, profiles/r03_column_route.txt: 1024 x 2048 runs 21 us per step here against 29 on the per-step route, 1024 x
-// 4096 56 against 42 - sixteen waves of one workgroup issue-bound on one CU)
-#define PF_COLUMN_MAX_N 2048
-// Which runs take it: self-contained runs (finalize: the last state's row is flushed by the same call), no state history,
-// a column that fits one workgroup.  pf_run_hints.route = PF_ROUTE_PER_STEP keeps everything on the per-step route (tests compare the two).
-static inline bool column_eligible(const pf_filter_args* A, const Geom& g, int64_t n_steps, int finalize) {
-    if (!finalize || n_steps < 1 || A->ring >= 3) return false;
-    if (A->hints.route == PF_ROUTE_PER_STEP) return false;
-    const int64_t max_n = A->hints.column_max_n > 0 ? A->hints.column_max_n : PF_COLUMN_MAX_N;
-    if (A->N > max_n || column_threads(A->N, PF_COLUMN_VEC) > 1024) return false;
-    return column_lds_bytes(A->N, A->model.dim, A->dtype == PF_F64 ? 8 : 4, PF_COLUMN_VEC) <= 64 * 1024;  // (the default dynamic-LDS limit)
-}
-
-template <typename T, int D>
-static int column_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps,
-                           hipStream_t st, float* kernel_ms) {
-    constexpr int VEC = PF_COLUMN_VEC;  // (four particles per lane whatever N: columns of N % 4 != 0 take the RAGGED instantiations)
-    FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
-    const int nt = column_threads(A->N, VEC);
-    const size_t lds = column_lds_bytes(A->N, D, sizeof(T), VEC);
-    const ObsFlags<T> flags(A, wl, t0, n_steps);
-    a.obs_dev = flags.dev;
-    if (flags.derive) flags.launch_derive(n_steps, st);
-    const KernelTimer timer(kernel_ms, st);
-    if (timer.failed) return timer.rc;
-    // the folded instantiations: float, four particles per lane - scalar states of the closed-form models and of Verhulst + SV,
-    // Lorenz-63 on whole 4-vectors (any workgroup size: the 256- or the 1024-thread bound); PF_ROUTE_COLUMN_GENERIC keeps the
-    // run-time kernel (tests compare the two)
-    auto with_column_folded = [&](auto&& f) {
-        if (A->hints.route == PF_ROUTE_COLUMN_GENERIC) return false;
-        if constexpr (sizeof(T) == 4 && D == 1) return with_folded<PF_HID_LINEAR, PF_HID_SINE_EM, PF_HID_OU, PF_HID_VERHULST_EM>(A, f);
-        if constexpr (sizeof(T) == 4 && D == 3) return A->N % VEC == 0 && with_folded<PF_HID_LORENZ63_EM>(A, f);
-        return false;
-    };
-    for (int64_t done = 0; done < n_steps;) {
-        const ColumnRun r = flags.piece(t0 + done, n_steps - done);
-        a.step = r.t0;
-        // k_fused_column with KIND / FILT / PROP folded (KIND = -1: the run-time kernel), at the 256- or the 1024-thread bound;
-        // columns of N % 4 != 0 particles take the RAGGED instantiations (the folded Lorenz-63 set has none)
-        // (a 512-thread bound would lift the scratch of the D > 1 kernels - but at > 128 VGPRs only ONE 8-wave workgroup fits
-        // a CU instead of two: 1024 x 2048 measured 33 us per step against 21)
-        auto launch = [&](auto user_c, auto kind_c, auto filt_c, auto prop_c) {
-            constexpr int KIND = decltype(kind_c)::value;
-            trace_launch(r.t0, (int)sizeof(T), D, VEC, A->resampler == PF_RESAMPLE_MULTINOMIAL ? 1 : 0, A->proposal, KIND >= 0 ? 1 : 0,
-                         /*SPEC*/ 9, KIND >= 0 ? KIND : 0, 0);
-            auto go = [&](auto tpb_c, auto rag_c) {
-                hipLaunchKernelGGL((k_fused_column<T, D, VEC, decltype(tpb_c)::value, decltype(user_c)::value, KIND, decltype(filt_c)::value,
-                                                   decltype(prop_c)::value, decltype(rag_c)::value>), dim3(g.B), dim3(nt), lds, st, a, r);
-            };
-            auto with_rag = [&](auto tpb_c) {
-                if constexpr (KIND < 0 || D == 1) {
-                    if (A->N % VEC != 0) return go(tpb_c, std::true_type{});
-                }
-                go(tpb_c, std::false_type{});
-            };
-            if (nt <= 256) with_rag(int_c<256>{});
-            else with_rag(int_c<1024>{});
-        };
-        if (!with_column_folded([&](auto kind_c, auto filt_c, auto prop_c) { launch(std::false_type{}, kind_c, filt_c, prop_c); })) {
-            if (A->model.hid_kind == PF_HID_USER_AFFINE) launch(std::true_type{}, int_c<-1>{}, int_c<-1>{}, int_c<-1>{});
-            else launch(std::false_type{}, int_c<-1>{}, int_c<-1>{}, int_c<-1>{});
-        }
-        done += r.n_steps;
-    }
-    timer.stop();
-    if (const int rc = timer.finish(n_steps)) return rc;  // (the run's one kernel, per time step)
-    return launch_status();
-}
-// the route's entries, one per arithmetic type, each in the unit that compiles its kernels
-int pf_run_column_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms);
-int pf_run_column_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms);
-#if defined(PF_TU_COLUMN_F32) || !defined(PF_TU_SPLIT)
-int pf_run_column_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms) {
-    return with_d3(A->model.dim, [&](auto d) { return column_run_impl<float, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms); });
-}
-#endif
-#if defined(PF_TU_COLUMN_F64) || !defined(PF_TU_SPLIT)
-int pf_run_column_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms) {
-    return with_d3(A->model.dim, [&](auto d) { return column_run_impl<double, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms); });
-}
-#endif
-
-// ---- the column-cluster route (pf_cluster.hpp): filters of 2 049 .. 16 384 particles, c workgroups per filter, one launch per
-// run and group of columns -------------------------------------------------------------------------------------------------------
-#define PFK_HOST_VEC 4  // particles per lane of the cluster kernels 
-#define PF_CLUSTER_INFEASIBLE (-1000)  // internal: the cluster kernel cannot be launched here (no launch was issued)
-static inline size_t cluster_lds_bytes(int D, size_t tsize) {
-    return (size_t)(PFK_WIN_P2 + D * PFK_WIN) * tsize + 2 * PFK_FOLD * sizeof(double);  // window planes | the folds of two states
-}
-// Opt-in (pf_run_hints.route == PF_ROUTE_CLUSTER): the members of a column wait for each other - a launch that cannot make
-// progress reports it through pf_filter_args.status instead of a result, and the caller re-issues the piece on the per-step
-// route (include/pf_amd.h: PF_ROUTE_CLUSTER); the all-zero hints of the C ABI never take it.
-static inline bool cluster_eligible(const pf_filter_args* A, const Geom& g, int64_t n_steps, int finalize) {
-    if (A->hints.route != PF_ROUTE_CLUSTER && A->hints.route != PF_ROUTE_CLUSTER_ALWAYS && A->hints.route != PF_ROUTE_CLUSTER_SPREAD) return false;
-    if (!finalize || n_steps < 1 || A->ring >= 3) return false;
-    if (A->N <= PF_CLUSTER_MIN_N || A->N > PF_CLUSTER_MAX_N || A->N % PFK_HOST_VEC != 0) return false;
-    if (A->resampler != PF_RESAMPLE_SYSTEMATIC || A->model.hid_kind == PF_HID_USER_AFFINE) return false;
-    // Where it pays (same-box A/Bs, profiles/r05_cluster_route.txt): a launch holds ~1 024 resident member workgroups (2^20
-    // particles) and larger batches run as consecutive launches of ~8.5 us per step each, while a per-step launch of 2^21+
-    // particles costs 33 us and grows by 3 us per 2^20 more - two launches' worth is the break-even
-    const int64_t members = ((A->N + PFK_TPB * PFK_HOST_VEC - 1) / (PFK_TPB * PFK_HOST_VEC)) * A->B;
-    if (A->hints.route == PF_ROUTE_CLUSTER && members > 2 * 1024) return false;
-    (void)g;
-    return true;
-}
-// resident workgroups of `kernel` on the current device: CUs x min(occupancy query, 6) - the query can be one block per CU high
-// near the SGPR-limited edges (MI355X_MICROARCH.md, "Residency and cooperative launch"); 6 is below every such edge
-// (asked once per kernel, LDS size and device: an online move is one such run per observation, and the three queries cost as much
-// host time as a launch)
-template <typename K> static inline int cluster_slots(K kernel, size_t lds) {
-    struct Seen { const void* k; size_t lds; int dev, slots; };
-    static Seen seen[32];
-    static std::atomic<int> n_seen{0};
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    const int have = n_seen.load(std::memory_order_acquire);
-    for (int i = 0; i < have; ++i)
-        if (seen[i].k == (const void*)kernel && seen[i].lds == lds && seen[i].dev == dev) return seen[i].slots;
-    int cus = 0, per_cu = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PFK_TPB, lds) != hipSuccess) return 0;
-    if (per_cu > 6) per_cu = 6;
-    std::lock_guard<std::mutex> lock(mu);
-    const int at = n_seen.load(std::memory_order_relaxed);
-    if (at < 32) {
-        seen[at] = Seen{(const void*)kernel, lds, dev, cus * per_cu};
-        n_seen.store(at + 1, std::memory_order_release);
-    }
-    return cus * per_cu;
-}
-template <typename T, int D>
-static int cluster_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps,
-                            hipStream_t st, float* kernel_ms, ThetaFold* theta) {
-    constexpr int VEC = PFK_HOST_VEC;
-    FusedArgs<T> a = make_fused_args<T>(A, g, wl, t0);
-    const size_t lds = cluster_lds_bytes(D, sizeof(T));
-    const ObsFlags<T> flags(A, wl, t0, n_steps);  // (derived by the launch that clears the first piece's records: k_zero_and_flags)
-    a.obs_dev = flags.dev;
-    // the caller numbers its launches (pf_run_hints.cluster_generation): tagged records, nothing to clear
-    bool numbered = A->hints.cluster_generation != 0 && A->status != nullptr && n_steps <= 32 * PFC_OBS_WORDS;
-    if (numbered) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) numbered = false;  // (a replay repeats the number)
-        (void)hipGetLastError();
-    }
-    const int c = (int)((A->N + PFK_TPB * VEC - 1) / (PFK_TPB * VEC));
-    const int nchunks = (int)((A->N + 64 * VEC - 1) / (64 * VEC));
-    int rc = PF_OK;
-    const KernelTimer timer(kernel_ms, st);
-    if (timer.failed) return timer.rc;
-    // the run on one instantiation of k_fused_cluster: KIND = -1 the run-time kernel, else the folded one
-    auto run = [&](auto kernel, int kind) {
-        // (nothing has been launched yet: PF_CLUSTER_INFEASIBLE sends the caller - filter_run_checked - to the per-step route)
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = PF_CLUSTER_INFEASIBLE;
-            return;
-        }
-        const int slots = cluster_slots(kernel, lds);
-        int per_launch = slots / c;  // columns whose members are all resident at once
-        if (per_launch >= 8) per_launch &= ~7;
-        if (per_launch < 1) {
-            rc = PF_CLUSTER_INFEASIBLE;
-            return;
-        }
-        unsigned char* clu = (unsigned char*)A->ws + wl.off_clu;
-        for (int64_t done = 0; done < n_steps;) {
-            const ColumnRun r = flags.piece(t0 + done, n_steps - done);
-            a.step = r.t0;
-            // fresh tags for this piece: error word + every record of the batch (a kernel, not a memset node - see k_zero_words)
-            // (only what this instantiation's records occupy: NG granule rows of 1 KB per column and parity, after the error word)
-            const size_t ng = ((size_t)(5 + 2 * D) * (sizeof(T) / 4) + 2 + 2) / 3;
-            size_t words = (256 + (size_t)2 * g.B * PF_CLUSTER_NG * 64 * 16) / sizeof(uint32_t);
-            if (g.B <= per_launch) words = (256 + (size_t)2 * g.B * ng * 64 * 16) / sizeof(uint32_t);  // (one group: its block is compact)
-            const bool with_flags = flags.derive && done == 0;
-            if (with_flags || !numbered) flags.launch_zero((uint32_t*)clu, words, with_flags, n_steps, st);
-            trace_launch(r.t0, (int)sizeof(T), D, VEC, 0, A->proposal, kind >= 0 ? 1 : 0, /*SPEC*/ 10, kind >= 0 ? kind : 0, c);
-            for (int b0 = 0; b0 < g.B; b0 += per_launch) {
-                ClusterRun cr;
-                cr.b0 = b0;
-                cr.nb = (g.B - b0 < per_launch) ? g.B - b0 : per_launch;
-                cr.nbp = (cr.nb + 7) & ~7;
-                cr.c = c;
-                cr.nchunks = nchunks;
-                // (numbered launches: the workspace's error word is never cleared - the caller's status word, which it clears itself, is both)
-                cr.err = numbered ? A->status : (int*)clu;
-                cr.status = numbered ? nullptr : A->status;
-                cr.tag_base = numbered ? (unsigned)(A->hints.cluster_generation & 0xFFFFF) * 4096u : 0u;
-                cr.patience = A->hints.cluster_patience != 0 ? A->hints.cluster_patience : PFK_SPIN_LIMIT;
-                cr.spread = A->hints.route == PF_ROUTE_CLUSTER_SPREAD ? 1 : 0;
-                cr.th = ClusterTheta{};
-                if (theta != nullptr && g.B <= per_launch && done + r.n_steps == n_steps && done == 0) {
-                    // (one launch carries the whole run and every column: its last column to finish does the theta update)
-                    cr.th.enabled = 1;
-                    cr.th.w = theta->w;
-                    cr.th.ll = theta->ll;
-                    cr.th.stats = theta->stats;
-                    cr.th.slot = (double*)theta->slot;
-                    cr.th.seq = (unsigned long long)theta->seq;
-                    cr.th.acc = theta->acc;
-                    cr.th.arrive = (unsigned*)clu + 16;
-                    theta->folded = 1;
-                }
-                cr.rec = clu + 256 + (size_t)b0 * 2 * PF_CLUSTER_NG * 64 * 16;  // (this group's [2][nb][NG][64] block)
-                hipLaunchKernelGGL(kernel, dim3((unsigned)(cr.nbp * c)), dim3(PFK_TPB), lds, st, a, r, cr);
-            }
-            done += r.n_steps;
-        }
-    };
-    // float runs of the built-in scalar closed-form models take KIND / FILT / PROP folded (as on the column route)
-    bool folded = false;
-    if constexpr (sizeof(T) == 4 && D == 1)
-        folded = with_folded<PF_HID_LINEAR, PF_HID_SINE_EM, PF_HID_OU>(A, [&](auto kind_c, auto filt_c, auto prop_c) {
-            run(k_fused_cluster<T, D, VEC, decltype(kind_c)::value, decltype(filt_c)::value, decltype(prop_c)::value>, decltype(kind_c)::value);
-        });
-    if (!folded) run(k_fused_cluster<T, D, VEC, -1, -1, -1>, -1);
-    if (rc != PF_OK) return rc;
-    timer.stop();
-    if ((rc = timer.finish(n_steps)) != PF_OK) return rc;
-    return launch_status();
-}
-int pf_run_cluster_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
-                       ThetaFold* theta);
-int pf_run_cluster_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
-                       ThetaFold* theta);
-#if defined(PF_TU_CLUSTER_F32) || !defined(PF_TU_SPLIT)
-int pf_run_cluster_f32(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
-                       ThetaFold* theta) {
-    return with_d3(A->model.dim, [&](auto d) { return cluster_run_impl<float, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms, theta); });
-}
-#endif
-#if defined(PF_TU_CLUSTER_F64) || !defined(PF_TU_SPLIT)
-int pf_run_cluster_f64(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, hipStream_t st, float* kernel_ms,
-                       ThetaFold* theta) {
-    return with_d3(A->model.dim, [&](auto d) { return cluster_run_impl<double, decltype(d)::value>(A, g, wl, t0, n_steps, st, kernel_ms, theta); });
-}
-#endif
-
-
-#ifndef PF_TU_NO_API
 // theta: pf_filter_observe's theta update, which the cluster route folds into its launch (null: none)
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
                               float* kernel_ms, ThetaFold* theta);
@@ -3166,4 +2027,3 @@ static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_ste
         });
     });
 }
-#endif  // !PF_TU_NO_API

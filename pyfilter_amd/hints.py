@@ -45,7 +45,7 @@ class RunHints:
 
     def cluster_takes(self, n, b, resampler_systematic=True):
         """Does a self-contained run of ``b`` filters of ``n`` particles take the column-cluster kernel (the library's rule,
-        ``pf_kernels.hip: cluster_eligible``)?  One launch per run - or two - with nothing for a hipGraph to replay."""
+        ``pf_host.hpp: cluster_eligible``)?  One launch per run - or two - with nothing for a hipGraph to replay."""
         route = self.kernel_route()
         if route not in (ROUTE_CLUSTER, ROUTE_CLUSTER_ALWAYS, ROUTE_CLUSTER_SPREAD) or not resampler_systematic:
             return False

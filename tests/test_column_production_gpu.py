@@ -34,7 +34,7 @@ MODEL_OF = {"lg": "lg1d", "sine": "sine", "ou": "ou_batched", "sv": "sv_batched"
 
 
 def _specialised(kind, n):
-    """Does a compile-time-specialised instantiation exist for this float32 run (pf_kernels.hip::column_run_impl)?"""
+    """Does a compile-time-specialised instantiation exist for this float32 run (pf_column.hip::column_run_impl)?"""
     if kind in ("lg", "sine", "ou", "sv"):
         return True  # scalar kinds: aligned or RAGGED, the 256- or the 1024-thread bound
     if kind == "lorenz":

@@ -41,6 +41,47 @@ def _lib_einval():
     return -1
 
 
+def _defined_dynamic_symbols(path):
+    """Names of the symbols an ELF64 (little-endian) shared object defines in its ``.dynsym``."""
+    import struct
+
+    with open(path, "rb") as f:
+        b = f.read()
+    assert b[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", b, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", b, 0x3A)
+    # (name, type, flags, addr, offset, size, link, info, addralign, entsize)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, kind, _, _, offset, size, link, _, _, _ in sections:
+        if kind != 11:  # SHT_DYNSYM
+            continue
+        strings = sections[link][4]
+        for at in range(offset, offset + size, 24):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", b, at)
+            if st_shndx != 0:  # (0 = SHN_UNDEF: an import)
+                names.add(b[strings + st_name:b.index(b"\0", strings + st_name)].decode())
+    return names
+
+
+def test_build_recipe_names_real_sources_and_the_library_exports_exactly_the_c_abi():
+    """``__graft_entry__.build_units`` is the one statement of which source makes which object: every entry names a source that
+    exists, no two entries write the same object, no ``.hip`` under ``csrc/`` is left out of the library - and what the linked
+    library exports under ``pf_`` is the C ABI (``_lib.EXPORTS``), nothing more: the units' internal entries stay C++ symbols."""
+    import __graft_entry__ as ge
+    from pyfilter_amd import _lib
+
+    units = ge.build_units("")
+    for src, _, _ in units:
+        assert os.path.isfile(os.path.join(ge.CSRC, src)), src
+    objects = [obj for _, _, obj in units]
+    assert len(set(objects)) == len(objects), objects
+    unused = {f for f in os.listdir(ge.CSRC) if f.endswith(".hip")} - {src for src, _, _ in units}
+    assert not unused, unused
+    exported = {s for s in _defined_dynamic_symbols(_lib.LIB_PATH) if s.startswith("pf_")}
+    assert exported == set(_lib.EXPORTS), (exported - set(_lib.EXPORTS), set(_lib.EXPORTS) - exported)
+
+
 def test_argument_validation_without_gpu():
     """Bad arguments are rejected before anything is launched (safe to call on a CPU-only box)."""
     from pyfilter_amd import _lib
@@ -510,7 +551,7 @@ def test_theta_particles_carry_their_derived_quantities_through_every_move():
 
 
 def test_hints_cluster_rule_mirrors_the_library():
-    """``HINTS.cluster_takes`` is the Python statement of ``pf_kernels.hip::cluster_eligible`` (which runs take the column-cluster
+    """``HINTS.cluster_takes`` is the Python statement of ``pf_host.hpp::cluster_eligible`` (which runs take the column-cluster
     kernel, i.e. the lean single-launch driver): 2 049 .. 16 384 particles, N % 4 == 0, systematic, two launches' worth of member
     workgroups under the default hints, any batch the workspace reserves records for under the tests' routes."""
     from pyfilter_amd.hints import ROUTE_CLUSTER, ROUTE_CLUSTER_ALWAYS, ROUTE_PER_STEP, RunHints

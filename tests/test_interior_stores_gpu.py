@@ -1,5 +1,5 @@
 """The per-step route stores an interior state's log-weights and ancestors only where somebody reads them
-(``FusedArgs::keep_state``, ``pf_fused.hpp: step_body`` stage 4; the rule: ``pf_kernels.hip: filter_run_impl``).
+(``FusedArgs::keep_state``, ``pf_fused.hpp: step_body`` stage 4; the rule: ``pf_step.hip: filter_run_impl``).
 
 * An APF step names new ancestors at every move, and the APF step after an observed one always resamples (apf.py:29-31) from the
   tile partials and the scans - it never loads the incoming log-weights.  Without a state history the log-weights are double

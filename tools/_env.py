@@ -1,6 +1,6 @@
 """Development tools only: translates THIS process's environment into the package's explicit switches - the package itself
 never reads the environment.  ``PF_AMD_LIB=<path>``: load an A/B or instrumented build of the library
-(tools/build_variant.sh, tools/pmc_stages.py); ``PF_NO_COLUMN / PF_COLUMN_GENERIC / PF_COLUMN_MAX_N / PF_TARGET_WGS /
+(tools/build_some.py --variant, tools/pmc_stages.py); ``PF_NO_COLUMN / PF_COLUMN_GENERIC / PF_COLUMN_MAX_N / PF_TARGET_WGS /
 PF_FORCE_SEARCH / PF_NO_FUSED_STEP / PF_NO_FUSED_BATCH / PF_NO_GRAPH``: ``pyfilter_amd.hints.HINTS``."""
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development tool: same-box A/B of two builds of the library (tools/build_variant.sh): alternates them ROUNDS times over the
+# Development tool: same-box A/B of two builds of the library (tools/build_some.py --variant): alternates them ROUNDS times over the
 # given tools/kbench.py configurations.   Usage: tools/ab.sh <libA.so> <libB.so> <rounds> <config> [<config> ...]
 A=$1; B=$2; R=$3; shift 3
 for r in $(seq 1 $R); do

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Development: where k_chunk_search (pf_systematic without a cdf) spends its time - cycle stamps of the middle workgroup of column 0,
-from the instrumented build: tools/build_variant.sh dev "-DPF_DEVTOOLS" main;  PF_AMD_LIB=.../libpfamd_dev.so python tools/chunk_search_stages.py [N] [B]"""
+from the instrumented build: python tools/build_some.py --variant dev --flags=-DPF_DEVTOOLS main;  PF_AMD_LIB=.../libpfamd_dev.so python tools/chunk_search_stages.py [N] [B]"""
 import ctypes as C
 import os
 import sys

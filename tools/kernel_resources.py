@@ -4,6 +4,7 @@ build - for the working tree, and against another revision when one is named: wh
     python tools/kernel_resources.py [unit] [rev]        unit: pf_main (default), pf_clu_f32, ... (tools/build_some.py's names)
 Round 6: indexing a small per-thread array by a run-time value had the compiler promote it to LDS - 18.5 KB in k_scan, for every
 caller - and nothing but this listing shows it."""
+import importlib.util
 import os
 import re
 import subprocess
@@ -15,12 +16,29 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 
-def descriptors(tree: str, flags, work: str):
-    src = os.path.join(tree, "pyfilter_amd", "csrc", "pf_kernels.hip")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, '-DPF_SOURCE_SHA256="x"', "-save-temps",
-                           "-o", os.path.join(work, "x.o")] + list(flags), cwd=work, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    text = open(os.path.join(work, "pf_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+def load_recipe(tree: str):
+    """``__graft_entry__`` of another tree - its ``build_units`` is that tree's recipe"""
+    spec = importlib.util.spec_from_file_location("graft_entry_of_rev", os.path.join(tree, "__graft_entry__.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def unit_of(recipe, name: str, work: str):
+    """(absolute source, flags, object under ``work``) of the unit called ``name`` in that recipe"""
+    for u in recipe.build_units(work):
+        if os.path.basename(u[-1])[:-2] == name:
+            if len(u) == 2:  # (revisions before the sources were split: one source, entries of (flags, object))
+                u = ("pf_kernels.hip",) + tuple(u)
+            return (os.path.join(recipe.CSRC, u[0]),) + tuple(u[1:])
+    raise SystemExit(f"no unit {name} in {recipe.ROOT}")
+
+
+def descriptors(unit, work: str):
+    cmd = ge.unit_command(unit, ["-save-temps"])
+    subprocess.check_call(cmd["args"], cwd=work, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)  # (the temporaries land in cwd)
+    stem = os.path.splitext(os.path.basename(unit[0]))[0]
+    text = open(os.path.join(work, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
     out = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S):
         num = lambda key: int(re.search(r"\.amdhsa_" + key + r"\s+(\d+)", m.group(2)).group(1))  # noqa: E731
@@ -39,17 +57,18 @@ def demangle(names):
 def main():
     unit = sys.argv[1] if len(sys.argv) > 1 else "pf_main"
     rev = sys.argv[2] if len(sys.argv) > 2 else None
-    flags = next(f for f, obj in ge.build_units("/tmp") if os.path.basename(obj)[:-2] == unit)
     with tempfile.TemporaryDirectory() as w1:
-        new = descriptors(ROOT, flags, w1)
+        new = descriptors(unit_of(ge, unit, w1), w1)
     old = None
     if rev:
         with tempfile.TemporaryDirectory() as tree, tempfile.TemporaryDirectory() as w2:
-            for path in subprocess.check_output(["git", "ls-tree", "-r", "--name-only", rev, "pyfilter_amd/csrc", "include"], cwd=ROOT, text=True).split():
+            paths = subprocess.check_output(["git", "ls-tree", "-r", "--name-only", rev, "pyfilter_amd/csrc", "include", "__graft_entry__.py"],
+                                            cwd=ROOT, text=True).split()
+            for path in paths:
                 os.makedirs(os.path.dirname(os.path.join(tree, path)), exist_ok=True)
                 with open(os.path.join(tree, path), "wb") as f:
                     f.write(subprocess.check_output(["git", "show", f"{rev}:{path}"], cwd=ROOT))
-            old = descriptors(tree, flags, w2)
+            old = descriptors(unit_of(load_recipe(tree), unit, w2), w2)  # (that revision's sources with that revision's flags)
     names = demangle(sorted(set(new) | set(old or {})))
     fmt = lambda r: f"LDS {r[0]:6d} B  scratch {r[1]:4d} B  VGPRs {r[2]:3d}"  # noqa: E731
     if old is None:

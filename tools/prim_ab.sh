@@ -1,5 +1,5 @@
 #!/bin/bash
-# per-kernel rocprofv3 averages of the stand-alone primitives for several variant libraries (tools/build_variant.sh):
+# per-kernel rocprofv3 averages of the stand-alone primitives for several variant libraries (tools/build_some.py --variant):
 # tools/prim_ab.sh name1 name2 ...   (shapes: 2^20 x 1, 65536 x 64, 4M x 1)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in "$@"; do
