@@ -15,7 +15,7 @@ import torch
 
 from ... import _lib as L
 from ... import ops
-from ...hints import HINTS
+from ...hints import HINTS, ROUTE_AUTO, ROUTE_CLUSTER, ROUTE_PER_STEP
 from ...resampling import multinomial, systematic
 from ...timeseries import AffineEulerMaruyama, StateSpaceModel, TimeseriesState
 from ...timeseries.models import pack_params
@@ -71,11 +71,11 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         self._draws = 0          # draw epoch: every new stream of random numbers (initial sample, fused run, online
                                  # move, step-by-step run) takes the next one - repeated calls are independent runs
         self._copies = 0
-        self._defer_status_once = False  # the next batch_filter leaves a cluster run's verification to its caller
-        self._per_step_once = False   # the next lean batch_filter takes the per-step route (see _batch_filter_lean)
-        self._online_cluster = False  # set by a caller that verifies its online moves (SMC2.step): see _filter_fused_single
-        self._watched_move = None     # (status word, redo) of the latest online move when it took the column-cluster kernel
         self._obs_cache = None   # (identity of y, host copy of its observed flags): re-filtering the same data costs no sync
+        self.cluster_fallbacks = 0  # column-cluster launches that gave up and were re-issued on the per-step route
+        self._time_kernels, self.kernel_ms = False, None  # measurement knob: fused runs go through pf_filter_run_timed -> kernel_ms
+        self._last_run = self._keep_planes = None  # what the latest fused run used (plan, tapes, seed, planes): keeps its buffers alive
+        self._u_gen = self._percol_cache = self._ffbs_u = None  # see _uniforms, _scale_per_column, set_smoothing_tape
 
     # ------------------------------------------------------------------------------------------------------------
     @property
@@ -284,7 +284,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         if self._ctx is not None and self._ctx.u_tape is not None:
             return self._ctx.u_tape[step]
         key = (self._run_seed, like.device)
-        gen = getattr(self, "_u_gen", None)
+        gen = self._u_gen
         if gen is None or gen[0] != key:
             g = torch.Generator(device=like.device)
             g.manual_seed(self._run_seed & 0x7FFFFFFFFFFFFFFF)
@@ -310,20 +310,24 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         """One filter move (``filters/base.py:188-221``).  Built-in models take the fused single-step path; anything
         else (user callables, custom resamplers, ``observe_every_step > 1``, recorded intermediary states) the
         reference's predict / correct sequence over the stand-alone kernels."""
+        return self._filter_move(y, correction, result)[0]
+
+    def _filter_move(self, y: torch.Tensor, correction: ParticleFilterCorrection, result: FilterResult = None, *, watched: bool = False):
+        """``filter()`` with ``(state, watch)`` for callers inside this package.  ``watched``: the caller reads the move's status word
+        with what it next waits for (SMC2.step), so the move may take the column-cluster kernel: ``watch = (status word, redo)``."""
         x = correction.timeseries_state.value
         if (not isinstance(y, torch.Tensor) or not self._fused_capable(x.device) or int(self._model.observe_every_step) != 1
                 or self._record_intermediary or not HINTS.fused_step):
-            return super().filter(y, correction, result=result)
-        if result is None:
-            return self._filter_fused_single(y, correction)
+            return super().filter(y, correction, result=result), None
         # (the run adds the move's log-likelihood to the result's running total itself - ``pf_filter_args.ll_total`` IS that
         # tensor - when it can be handed over as it is: one elementwise launch per online move less)
-        new = self._filter_fused_single(y, correction, ll_into=result._loglikelihood)
-        # (a watched move - ``_online_cluster`` - leaves the accumulation to its caller's pf_theta_step: ``_watched_move``)
-        result.append(new, _ll_accumulated=self._ll_accumulated or self._watched_move is not None)
-        return new
+        new, ll_added, watch = self._filter_fused_single(y, correction, None if result is None else result._loglikelihood, watched)
+        if result is not None:  # (a watched move leaves the accumulation to its caller's pf_theta_step)
+            result.append(new, ll_added=ll_added or watch is not None)
+        return new, watch
 
-    def _filter_fused_single(self, y: torch.Tensor, state: ParticleFilterCorrection, ll_into: torch.Tensor = None) -> ParticleFilterCorrection:
+    def _filter_fused_single(self, y: torch.Tensor, state: ParticleFilterCorrection, ll_into: torch.Tensor = None, watched: bool = False):
+        """One fused move: ``(new state, the kernels added its log-likelihood to ``ll_into``, watch)``."""
         # (the host's share of an online move is what SMC2.step() / a driver's loop over filter() run at - every torch call here
         # costs 1 - 1.5 us: the buffers of a state this method produced are remembered with it, a plan keeps what does not
         # change between moves, pointers into the move's statistics block are computed, not sliced)
@@ -350,10 +354,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         plan = self._single_last
         if (plan is None or plan.n != n or plan.b != b or plan.d != d or plan.o != o or plan.rows != rows or plan.dtype != dtype
                 or plan.device != device or plan.rs_kind != rs_kind or plan.thr != thr or plan.kind is not kind):
-            key = (n, b, d, o, rows, dtype, device, self._FILTER_KIND, self._proposal._KERNEL_PROPOSAL, rs_kind, thr)
-            plan = self._single_plans.get(key)
-            if plan is None:
-                plan = self._single_plans[key] = _SingleStepPlan(self, kind, n, b, d, o, rows, dtype, device)
+            plan = self._single_plan(kind, n, b, d, o, rows, dtype, device)
             plan.rs_kind, plan.thr, plan.kind = rs_kind, thr, kind
             self._single_last = plan
         t_start = int(ts_in.time_index)
@@ -374,16 +375,13 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         a = plan.args
         # An online move is not verified by anybody who waits for it - the caller may never look at the device again before the
         # next move - so it takes the column-cluster kernel (whose launches can give up, hints.py) only on behalf of a caller
-        # that reads the move's status word with the next thing it waits for: SMC2.step() (``_online_cluster``; the word travels
+        # that reads the move's status word with the next thing it waits for: SMC2.step() (``watched``; the word travels
         # through pf_theta_step into the host slot it polls).  Everybody else's moves of that size stay on the per-step route.
-        verified = self._online_cluster and HINTS.kernel_route() == 3 and HINTS.cluster_takes(n, b, rs_kind == L.RESAMPLE_SYSTEMATIC)
+        verified = watched and HINTS.kernel_route() == ROUTE_CLUSTER and HINTS.cluster_takes(n, b, rs_kind == L.RESAMPLE_SYSTEMATIC)
         stream = L.stream_ptr()
         hk = (HINTS.key(), verified, stream)  # (the stream: a resumed piece relies on stream order behind the previous one)
-        if plan.hints_key != hk or a.hints.prepare_next:
-            HINTS.fill(a)
-            if a.hints.route == 3 and not verified:
-                a.hints.route = 0  # PF_ROUTE_AUTO
-            plan.hints_key = hk
+        if plan.hints_key != hk or a.hints.prepare_next:  # (unchanged key: the block holds these values - nothing is written)
+            plan.write_hints(hk, ROUTE_AUTO if (HINTS.kernel_route() == ROUTE_CLUSTER and not verified) else None)
         if verified:
             ll_into = None  # (the running total is accumulated by pf_theta_step, under the same status word: SMC2State.append)
         a.model.params = ctx.params.data_ptr()
@@ -408,7 +406,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         # row m is this move's.  Anything else - a state somebody replaced or edited, another plan's, a rejuvenated filter set -
         # starts a fresh run at piece 0.
         m = 0
-        per_step_route = (not verified) and (HINTS.route == 1 or (a.hints.route == 0 and n > (HINTS.column_max_n or 2048)))
+        per_step_route = (not verified) and (HINTS.route == ROUTE_PER_STEP or (a.hints.route == ROUTE_AUTO and n > (HINTS.column_max_n or 2048)))
         chain = plan.chain
         if (per_step_route and chain is not None and chain[1] is x_in and chain[2] is lw_in and chain[3] == x_in._version
                 and chain[4] == lw_in._version and chain[5] == hk):
@@ -426,9 +424,9 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         db = d * b * es
         a.means, a.vars = stats_ptr - m * db, stats_ptr + 2 * db - m * db
         a.ll_steps = stats_ptr + 4 * db - m * b * es
-        self._ll_accumulated = (ll_into is not None and ll_into.device == device and ll_into.dtype == dtype and ll_into.numel() == b
-                                and ll_into.is_contiguous())
-        a.ll_total = ll_into.data_ptr() if self._ll_accumulated else stats_ptr + 4 * db + b * es
+        ll_added = (ll_into is not None and ll_into.device == device and ll_into.dtype == dtype and ll_into.numel() == b
+                    and ll_into.is_contiguous())
+        a.ll_total = ll_into.data_ptr() if ll_added else stats_ptr + 4 * db + b * es
         z_tape = u_tape = None
         if ctx.z_tape is not None:
             z_tape = ctx.z_tape[t_start:t_start + 1].contiguous()
@@ -438,50 +436,48 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         # no uniform tape: every workgroup draws its column's u (Philox)
         a.z_tape = None if z_tape is None else z_tape.data_ptr() - m * d * b * n * es
         a.u_tape = None if u_tape is None else u_tape.data_ptr() - m * b * es
-        plan.generation = g_ = plan.generation % 0xFFFFF + 1  # (numbered cluster launches: tagged records, no clearing launch)
-        a.hints.cluster_generation = g_
+        a.hints.cluster_generation = plan.next_generation()
         L.check(plan.run(plan.args_ref, m, 1, 1, stream), "pf_filter_run")
         if per_step_route:
             plan.chain = (m, x_out, lw_out, x_out._version, lw_out._version, hk)
         self._last_run = dict(plan=plan, z=z_tape, u=u_tape, ws=plan.ws, seed_eff=a.seed, piece=m,
                               keep=(x_in, lw_in, y_dev, ctx.params, planes))
-        self._watched_move = None
+        watch = None
         if verified:
             pool_row = plan._pool[0][plan._pool_next - 1]
 
-            def redo():
-                """The same move again on the per-step route, into the same tensors (the argument block still describes it)."""
-                self._cluster_gave_up(plan)
+            def restore():
                 if not apf:
                     anc.copy_(state.ancestors32().reshape(b, n))
                 pool_row[4 * d + 1].zero_()  # (the move's own total: accumulated, not written)
-                a.hints.route, plan.hints_key = 1, None  # PF_ROUTE_PER_STEP (the next move re-writes the hints)
-                L.check(plan.run(plan.args_ref, 0, 1, 1, L.stream_ptr()), "pf_filter_run")
 
-            self._watched_move = (plan.status, redo)
+            # (redo: the same move again on the per-step route, into the same tensors - the argument block still describes it)
+            watch = (plan.status, lambda: self._reissue_per_step(plan, restore, 0, 1))
 
         x_view, w_view = plan.state_views(x_out, lw_out, batched, has_event)
         new = ParticleFilterCorrection(TimeseriesState(t_start + 1, x_view, self._model.hidden.event_shape), w_view, ll_new, None,
                                        _moments=(mean_new, var_new), _anc32=(anc, batched))
         new._soa = (x_view, w_view, x_out, lw_out)
-        return new
+        return new, ll_added, watch
 
     def batch_filter(self, y, bar=True, init_state=None) -> FilterResult:
-        """``self._defer_status_once`` (set by callers inside this package that never wait for a run by itself - PMMH moves): a run
-        that took the column-cluster kernel is NOT verified before it is handed back; ``result._cluster_watch = (status word,
-        plan)`` lets the caller look where it next waits for the device (a launch that gave up leaves NaN log-likelihoods: a
-        rejected proposal)."""
+        return self._batch_filter(y, init_state, bar=bar)[0]
+
+    def _batch_filter(self, y, init_state=None, *, bar=False, defer_status=False, per_step=False):
+        """``batch_filter`` with ``(result, watch)`` for callers inside this package.  ``defer_status`` (callers that never wait for a
+        run by itself - PMMH moves): a run that took the column-cluster kernel is NOT verified before it is handed back; ``watch =
+        (status word, plan)`` lets the caller look where it next waits for the device (a launch that gave up leaves NaN log-likelihoods:
+        a rejected proposal).  ``per_step``: a single-launch run takes the per-step route (the repeat of a run whose launch gave up)."""
         assert self._model is not None, "Model has not been initialized!"
-        _defer_status, self._defer_status_once = self._defer_status_once, False
         device, _ = self._device_dtype()
         if (not self._fused_capable(device) or not isinstance(y, torch.Tensor)
                 or not HINTS.fused_batch
                 or (self._kernel_kind().is_user and FilterResult.states_kept(self.record_states) != 1)):
             # (a user-defined affine process with recorded states: the driver's loop over fused single steps)
-            return super().batch_filter(y, bar=bar, init_state=init_state)
+            return super().batch_filter(y, bar=bar, init_state=init_state), None
         if self._single_launch_run(y):
-            return self._batch_filter_lean(y, init_state, defer_status=_defer_status)
-        return self._batch_filter_fused(y, init_state)
+            return self._batch_filter_lean(y, init_state, defer_status, per_step)
+        return self._batch_filter_fused(y, init_state), None
 
     def _single_launch_run(self, y) -> bool:
         """A run the library issues as ONE launch of the column-persistent kernel (filters of <= 2 048 particles) - or one or two
@@ -489,22 +485,20 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         recorded but the moments: there is no launch sequence for a hipGraph to replay, so the persistent plan of the general
         driver (its buffers, staging copies and per-shape cache - PMMH re-filters a data set of another length at every
         rejuvenation) only costs host time."""
-        return (y.shape[0] > 0 and FilterResult.states_kept(self.record_states) == 1 and not getattr(self, "_time_kernels", False)
+        return (y.shape[0] > 0 and FilterResult.states_kept(self.record_states) == 1 and not self._time_kernels
                 and not self._move_by_move and not self._kernel_kind().is_user and int(self._model.observe_every_step) == 1
-                and (HINTS.direct or (HINTS.route != 1 and self._base_particles[0] <= (HINTS.column_max_n or 2048))
+                and (HINTS.direct or (HINTS.route != ROUTE_PER_STEP and self._base_particles[0] <= (HINTS.column_max_n or 2048))
                      or HINTS.cluster_takes(self._base_particles[0], self.batch_shape[0] if self._batched else 1,
                                             self._resampler_kind() == L.RESAMPLE_SYSTEMATIC))
                 and self._ctx_tapes_none())
 
-    def _batch_filter_lean(self, y: torch.Tensor, init_state=None, defer_status: bool = False) -> FilterResult:
+    def _batch_filter_lean(self, y: torch.Tensor, init_state, defer_status: bool, per_step: bool):
         state = init_state if init_state is not None else self.initialize()
         result = FilterResult(state, self.record_states, self.record_moments, _defer_moments=True)
-        per_step, self._per_step_once = self._per_step_once, False  # (a caller repeating a run whose cluster launch gave up)
         blk, _, _ = self._filter_block_lean(y, state, None, None, host_u=True, defer_status=defer_status, per_step=per_step)
-        result._cluster_watch = (blk.status, blk.plan) if blk.status is not None else None
         result._extend_fused(blk.filter_means, blk.filter_variance, blk.loglikelihood, blk.latest_state)
         self._last_run["rows"] = (blk.filter_means, blk.filter_variance)
-        return result
+        return result, ((blk.status, blk.plan) if blk.status is not None else None)
 
     def _observed_flags(self, y: torch.Tensor, y_dev: torch.Tensor) -> torch.Tensor:
         """Host copy of "observation k carries information" (not all-NaN), one byte per observation.  The launch loop
@@ -539,7 +533,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         if (not self._fused_capable(x.device) or int(self._model.observe_every_step) != 1 or self._record_intermediary
                 or self._kernel_kind().is_user):
             return None
-        if (FilterResult.states_kept(self.record_states) == 1 and not getattr(self, "_time_kernels", False)
+        if (FilterResult.states_kept(self.record_states) == 1 and not self._time_kernels
                 and not self._move_by_move and self._ctx_tapes_none()):
             return self._filter_block_lean(y, state, observed, replay, per_step=per_step, defer_status=defer_status)
         res = self._batch_filter_fused(y, state._restarted(), observed=observed, replay=replay)
@@ -572,7 +566,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         # (a callable typically hands back the same parameter tensor move after move: the small array is built once per
         # storage / in-place version, not per move - four tiny launches a host-bound small filter would feel)
         key = (scale.data_ptr(), scale._version, tuple(scale.stride()), dtype)
-        cached = getattr(self, "_percol_cache", None)
+        cached = self._percol_cache
         if cached is not None and cached[0] == key:
             return cached[1]
         out = self._scale_rows(scale, dtype)
@@ -596,16 +590,33 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         """The fast driver of an observation-by-observation loop over ``result`` (``_OnlineRun``), or None where it does not apply."""
         return _OnlineRun(self, result) if _OnlineRun.applies(self, result) else None
 
+    def _single_plan(self, kind, n, b, d, o, rows, dtype, device):
+        """The ``_SingleStepPlan`` of a shape: the online move and the block route share it, and so one argument block."""
+        key = (n, b, d, o, rows, dtype, device, self._FILTER_KIND, self._proposal._KERNEL_PROPOSAL,
+               self._resampler_kind(), float(self._resample_threshold))
+        plan = self._single_plans.get(key)
+        if plan is None:
+            plan = self._single_plans[key] = _SingleStepPlan(self, kind, n, b, d, o, rows, dtype, device)
+        return plan
+
     def _cluster_gave_up(self, plan):
         """A column-cluster launch of ``plan`` reported that it could not make progress: the word is cleared for the next
         run and the event is announced once per filter object (the caller re-issues the piece on the per-step route)."""
         plan.status.zero_()
-        self.cluster_fallbacks = getattr(self, "cluster_fallbacks", 0) + 1
+        self.cluster_fallbacks += 1
         if self.cluster_fallbacks == 1:
             import warnings
 
             warnings.warn("pyfilter_amd: a column-cluster launch gave up waiting for its sibling workgroups (the device was held "
                           "by other work); the piece is re-issued on the per-step route - same draws, same results")
+
+    def _reissue_per_step(self, plan, restore, t0: int, n_steps: int):
+        """The piece ``(t0, n_steps)`` of ``plan``, whose column-cluster launch gave up, again on the per-step route: ``restore()`` puts
+        back what the launch consumed of its inputs, the argument block still describes the piece.  Same draws, same numbers."""
+        self._cluster_gave_up(plan)
+        restore()
+        plan.write_hints(None, ROUTE_PER_STEP)  # (no key: whoever runs on this block next writes its own hints)
+        L.check(plan.run(plan.args_ref, t0, n_steps, 1, L.stream_ptr()), "pf_filter_run")
 
     def _filter_block_lean(self, y: torch.Tensor, state: ParticleFilterCorrection, observed, replay, host_u: bool = False,
                            per_step: bool = False, defer_status: bool = False):
@@ -632,11 +643,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         if rows not in (1, b):
             raise L.PfAmdError(f"observations of shape {tuple(y.shape)} do not broadcast against batch {b}")
         flags = (observed if observed is not None else self._observed_flags(y, y_dev)).contiguous()
-        key = (n, b, d, o, rows, dtype, device, self._FILTER_KIND, self._proposal._KERNEL_PROPOSAL,
-               self._resampler_kind(), float(self._resample_threshold))
-        plan = self._single_plans.get(key)
-        if plan is None:
-            plan = self._single_plans[key] = _SingleStepPlan(self, kind, n, b, d, o, rows, dtype, device)
+        plan = self._single_plan(kind, n, b, d, o, rows, dtype, device)
         plan.chain = None  # (the block's run rewrites the workspace an online move's resume token points into)
         if plan.xl is None:  # the run's other state slot (the kernels alternate between two)
             plan.xl = torch.empty((d + 1, b, n), device=device, dtype=dtype)
@@ -665,9 +672,8 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
 
         load_state()
         a = plan.args
-        HINTS.fill(a)
-        if per_step:
-            a.hints.route = 1  # PF_ROUTE_PER_STEP: the re-issue of a piece whose column-cluster launch gave up
+        # (no key: an online move on this plan, i.e. this argument block, writes its own again.  ``per_step``: a re-issue after a give-up)
+        plan.write_hints(None, ROUTE_PER_STEP if per_step else None)
         a.model.params = ctx.params.data_ptr()
         a.y, a.y_rows = y_dev.data_ptr(), rows
         a.observed, a.observed_dev = flags.data_ptr(), None
@@ -687,19 +693,15 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         a.anc = anc.data_ptr()
         a.means, a.vars = rows_buf[0].data_ptr(), rows_buf[1].data_ptr()
         a.ll_steps, a.ll_total = ll.data_ptr(), ll[steps].data_ptr()
-        plan.generation = a.hints.cluster_generation = plan.generation % 0xFFFFF + 1
-        L.check(L.load().pf_filter_run(C.byref(a), 0, steps, 1, L.stream_ptr()), "pf_filter_run")
+        a.hints.cluster_generation = plan.next_generation()
+        L.check(plan.run(plan.args_ref, 0, steps, 1, L.stream_ptr()), "pf_filter_run")
         # A column-cluster launch reports through the plan's status word when it could not make progress (include/pf_amd.h:
         # PF_ROUTE_CLUSTER).  ``batch_filter`` looks at it here (one small device -> host read per run); a caller that pipelines
         # blocks (SMC2.fit) takes the word with the block (``defer_status``), reads it with the block's statistics and asks for
         # the block again with ``per_step = True`` - a replay on the same draws, so the numbers are the one-piece run's.
         watched = (not per_step) and HINTS.cluster_takes(n, b, self._resampler_kind() == L.RESAMPLE_SYSTEMATIC)
         if watched and not defer_status and int(plan.status.item()) != 0:
-            self._cluster_gave_up(plan)
-            load_state()
-            ll.zero_()
-            a.hints.route = 1
-            L.check(L.load().pf_filter_run(C.byref(a), 0, steps, 1, L.stream_ptr()), "pf_filter_run")
+            self._reissue_per_step(plan, lambda: (load_state(), ll.zero_()), 0, steps)
         self._last_run = dict(plan=plan, z=None, u=u_tape, ws=plan.ws, seed_eff=seed_eff, ll_steps=ll[:steps],
                               keep=(x_in, lw_in, y_dev, flags, ctx.params))
 
@@ -765,7 +767,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             wanted = reported if keep_states is None else reported[-keep_states:]
             ring = max(3, steps - wanted[0] + 1)  # slots for the states wanted[0] .. steps
         taped = ctx.z_tape is not None or ctx.u_tape is not None
-        use_graph = ((not taped) and not ring and replay is None and not getattr(self, "_time_kernels", False)
+        use_graph = ((not taped) and not ring and replay is None and not self._time_kernels
                      and HINTS.graph and not kind.is_user and not self._move_by_move)
         key = (n, b, d, o, steps, rows, dtype, device, self._FILTER_KIND, self._proposal._KERNEL_PROPOSAL,
                self._resampler_kind(), self._seed, float(self._resample_threshold), observed_host.numpy().tobytes(), HINTS.key())
@@ -773,7 +775,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         # per move the callable's own torch launches and the library's kernel - is captured ONCE as a hipGraph (torch.cuda.graph)
         # and replayed: the callable's launches are a few microseconds of kernel each, issued eagerly they set the pace of a move
         user_graph = (kind.is_user and bool(getattr(self._model.hidden, "graph_callable", False)) and (not taped) and not ring
-                      and replay is None and not getattr(self, "_time_kernels", False) and HINTS.graph
+                      and replay is None and not self._time_kernels and HINTS.graph
                       and not isinstance(self._move_by_move, (list, tuple)))
         plan = self._fused_plans.get(key) if (use_graph or user_graph) else None
         if plan is None:
@@ -799,7 +801,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         word = (seed_eff - self._seed) & _M64
         plan.epoch.fill_(word - (1 << 64) if word >= (1 << 63) else word)
         a = plan.args
-        HINTS.fill(a)  # (a cached plan was keyed by them; a fresh one takes the current ones)
+        plan.write_hints(None)  # (a cached plan was keyed by them; a fresh one takes the current ones)
         z_tape = u_tape = None
         if ctx.z_tape is not None:
             z_tape = ctx.z_tape[t_start:t_start + steps].contiguous()
@@ -830,7 +832,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             # moves run without the bookkeeping launch and - SISR - the successor without the reduce launch
             # (pf_run_hints.resume).  Filters small enough for the column kernel keep self-contained moves (finalize = 1
             # is what makes a call eligible for that one-launch route).
-            chained = kind.is_user and (HINTS.route == 1 or n > (HINTS.column_max_n or 2048))
+            chained = kind.is_user and (HINTS.route == ROUTE_PER_STEP or n > (HINTS.column_max_n or 2048))
             keep = []
             # An APF move with the optimal proposal and ONE transition scale per filter can prepare its successor's first-stage
             # weights itself, like every step of a built-in model's run (pf_run_hints.prepare_next: they read the new particle
@@ -911,7 +913,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
                 a.user_loc, a.user_scale = plan.user_loc.data_ptr(), plan.user_scale.data_ptr()
                 a.user_scale_per_column, a.hints.resume, a.hints.prepare_next = 0, 0, 0
                 self._keep_planes = keep
-        elif getattr(self, "_time_kernels", False):
+        elif self._time_kernels:
             kms = (C.c_float * 3)()
             L.check(lib.pf_filter_run_timed(C.byref(a), 0, steps, 1, L.stream_ptr(), kms), "pf_filter_run_timed")
             self.kernel_ms = tuple(kms)
@@ -930,10 +932,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         # that size take the lean driver: a launch that gave up is re-issued on the per-step route there and here alike)
         if (not ring and not kind.is_user and HINTS.cluster_takes(n, b, self._resampler_kind() == L.RESAMPLE_SYSTEMATIC)
                 and int(plan.status.item()) != 0):
-            self._cluster_gave_up(plan)
-            load_state()
-            a.hints.route = 1  # PF_ROUTE_PER_STEP
-            L.check(lib.pf_filter_run(C.byref(a), 0, steps, 1, L.stream_ptr()), "pf_filter_run")
+            self._reissue_per_step(plan, load_state, 0, steps)
         self._last_run = dict(plan=plan, z=z_tape, u=u_tape, ws=plan.ws, seed_eff=seed_eff)  # keep device buffers alive
 
         # ---- hand the results over in the reference's shapes (copies: a cached plan's buffers are reused) ------------
@@ -1020,7 +1019,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         ctx = self._ensure_context()
         if ctx is not None and on_gpu and not ctx.kind.is_user and ctx.kind.hid_kind != L.HID_LINEAR_MAT:
             x_hist, w_hist, _ = self._history(states)
-            u = getattr(self, "_ffbs_u", None)
+            u = self._ffbs_u
             if u is not None:
                 s1 = len(states) - 1
                 u = u.to(device=x_hist.device, dtype=x_hist.dtype).reshape(s1, x_hist.shape[3], x_hist.shape[2]).permute(0, 2, 1).contiguous()
@@ -1090,8 +1089,7 @@ class _OnlineRun:
         self._theta_step, self._observe = self._lib.pf_theta_step, self._lib.pf_filter_observe
         self._code = L.dtype_code(x.dtype)
         self._ll_ptr, self._stats_ptr = self.ll.data_ptr(), self.stats.data_ptr()
-        self._status_ptr = plan.status.data_ptr()
-        self.hints_key, self._stream = None, None
+        self._stream = None
 
     @staticmethod
     def applies(filt, result) -> bool:
@@ -1149,9 +1147,8 @@ class _OnlineRun:
         if y.dtype != self.dtype or not y.is_cuda or not y.is_contiguous():
             y = y.to(device=self.device, dtype=self.dtype).contiguous()
         hk = HINTS.key()
-        if self.hints_key != hk:
-            HINTS.fill(a)
-            self.hints_key = hk
+        if plan.hints_key != hk:
+            plan.write_hints(hk)
         m, es, b = self.m, self.es, self.b
         a.model.params = ctx.params.data_ptr()
         a.y = y.data_ptr() - m * self.o * es
@@ -1161,7 +1158,7 @@ class _OnlineRun:
             ut = None if ctx.u_tape is None else ctx.u_tape[self.t]
             a.z_tape = None if zt is None else zt.data_ptr() - m * self.d * b * self.n * es
             a.u_tape = None if ut is None else ut.data_ptr() - m * b * es
-        plan.generation = a.hints.cluster_generation = plan.generation % 0xFFFFF + 1
+        a.hints.cluster_generation = plan.next_generation()
         total = self.result._loglikelihood
         seq = slot.seq + 1
         # the move and the theta update in one call (pf_filter_observe = pf_filter_run + pf_theta_step under the move's status word)
@@ -1170,11 +1167,7 @@ class _OnlineRun:
         slot.seq = seq
         pair = slot.wait()
         if slot.status:  # a column-cluster launch gave up (nothing was updated): the piece again on the per-step route, same draws
-            filt._cluster_gave_up(plan)
-            self.scratch_total.zero_()
-            a.hints.route = 1
-            L.check(plan.run(plan.args_ref, m, 1, 1, stream), "pf_filter_run")
-            self.hints_key = None
+            filt._reissue_per_step(plan, self.scratch_total.zero_, m, 1)
             seq = slot.seq + 1
             L.check(self._theta_step(w.data_ptr(), self._ll_ptr + m * b * es, b, self._code, self._stats_ptr + 2 * m * es, slot.ptr, seq,
                                      total.data_ptr(), None, stream), "pf_theta_step")
@@ -1229,6 +1222,23 @@ class _BlockResult:
         return [self.latest_state]
 
 
+def _new_args(plan, filt, kind, params, n, b, dtype):
+    """``plan.args`` (with ``args_ref`` / ``run`` to issue them) of a new plan, filled with what does not depend on the driver: model,
+    filter / proposal / resampler, type, sizes, threshold, base seed, the plan's ``cdf`` / ``pos`` scratch, workspace and status word."""
+    a = L.PfFilterArgs()
+    a.model = ops.make_model_struct(kind, params)
+    a.filter, a.proposal, a.resampler = filt._FILTER_KIND, filt._proposal._KERNEL_PROPOSAL, filt._resampler_kind()
+    a.dtype = L.dtype_code(dtype)
+    a.N, a.B = n, b
+    a.ess_threshold = float(filt._resample_threshold) / float(n)
+    a.seed = filt._seed
+    a.cdf, a.pos = plan.cdf.data_ptr(), plan.pos.data_ptr()
+    a.ws, a.ws_bytes = plan.ws.data_ptr(), plan.ws.numel()
+    a.status = plan.status.data_ptr()
+    plan.args, plan.args_ref, plan.run, plan.hints_key = a, C.byref(a), L.load().pf_filter_run, None
+    return a
+
+
 class _SingleStepPlan:
     """Scratch + launch arguments of the fused *single-step* move behind ``filter()`` (the online / SMC^2 entry point):
     the kernels read the incoming state's own buffers and write freshly allocated ones that become the new state -
@@ -1239,32 +1249,32 @@ class _SingleStepPlan:
         self.pos = torch.empty((b, n), device=device, dtype=dtype)
         self.ws = L.new_workspace(n, b, device)
         self.status = torch.zeros(1, device=device, dtype=torch.int32)  # pf_filter_args.status: sticky, cleared by _cluster_gave_up
-        self.rows = rows
         self.xl = None  # (``_filter_block_lean``: the second state slot of a multi-move run, allocated on first use)
         self.u_gen = None
-        a = L.PfFilterArgs()
-        a.model = ops.make_model_struct(kind, filt._ctx.params)
-        a.filter, a.proposal, a.resampler = filt._FILTER_KIND, filt._proposal._KERNEL_PROPOSAL, filt._resampler_kind()
-        a.dtype = L.dtype_code(dtype)
-        a.N, a.B = n, b
-        a.ess_threshold = float(filt._resample_threshold) / float(n)
-        a.seed = filt._seed
-        a.cdf, a.pos = self.cdf.data_ptr(), self.pos.data_ptr()
-        a.y, a.y_rows, a.observed, a.observed_dev = None, rows, None, None  # (flags: derived from y by the run)
-        a.step_counter = None
-        a.ws, a.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        a.status = self.status.data_ptr()
-        self.args = a
-        self.args_ref = C.byref(a)
-        self.run = L.load().pf_filter_run
+        a = _new_args(self, filt, kind, filt._ctx.params, n, b, dtype)
+        a.y, a.y_rows, a.observed, a.observed_dev, a.step_counter = None, rows, None, None, None  # (flags: derived from y by the run)
         self.n, self.b, self.d, self.o, self.rows, self.dtype, self.device = n, b, d, o, rows, dtype, device
-        self.kind, self.rs_kind, self.thr, self.hints_key = kind, None, None, None
+        self.kind, self.rs_kind, self.thr = kind, None, None
         self.elem_size = torch.empty((), dtype=dtype).element_size()
         self._pool = None
         self._pool_next = 0
         self._view_geo = None
         self.generation = 0  # pf_run_hints.cluster_generation of the latest cluster launch on self.ws (zero-filled: new_workspace)
         self.chain = None  # the resume token: (piece, x_out, lw_out, their versions, hints) of the latest per-step-route online move
+
+    def write_hints(self, key, route=None):
+        """The ONE writer of the kernel-side choices in a plan's argument block: the current ``HINTS`` (``route``: instead of theirs),
+        recorded as belonging to ``key``.  A driver that caches "the block holds my hints" compares ``hints_key`` with its own key;
+        every other writer passes None - no driver's key survives another driver's write."""
+        HINTS.fill(self.args)
+        if route is not None:
+            self.args.hints.route = route
+        self.hints_key = key
+
+    def next_generation(self) -> int:
+        """The number of the next cluster launch on ``self.ws`` (1 .. 0xFFFFF, round and round: tagged records, no clearing launch)."""
+        self.generation = self.generation % 0xFFFFF + 1
+        return self.generation
 
     _STATS_POOL = 64
 
@@ -1342,26 +1352,19 @@ class _FusedPlan:
         self.user_graph = self.user_graph_sig = self.user_graph_keep = None  # torch.cuda.CUDAGraph of a user-affine run (graph_callable)
         self.user_graph_failed = False
 
-        a = L.PfFilterArgs()
-        a.model = ops.make_model_struct(kind, self.params)
-        a.filter, a.proposal, a.resampler = filt._FILTER_KIND, filt._proposal._KERNEL_PROPOSAL, filt._resampler_kind()
-        a.dtype = L.dtype_code(dtype)
-        a.N, a.B = n, b
-        a.ess_threshold = float(filt._resample_threshold) / float(n)
-        a.seed = filt._seed
+        a = _new_args(self, filt, kind, self.params, n, b, dtype)
         a.x[0], a.x[1] = self.x[0].data_ptr(), self.x[1].data_ptr()
         a.logw[0], a.logw[1] = self.logw[0].data_ptr(), self.logw[1].data_ptr()
-        a.anc, a.cdf, a.pos = self.anc.data_ptr(), self.cdf.data_ptr(), L.ptr(self.pos)
+        a.anc = self.anc.data_ptr()
         a.y, a.y_rows, a.observed = self.y.data_ptr(), rows, observed_host.data_ptr()
         a.z_tape, a.u_tape = None, None
         a.means, a.vars = self.means.data_ptr(), self.vars.data_ptr()
         a.ll_steps, a.ll_total = self.ll_steps.data_ptr(), self.ll_total.data_ptr()
         a.step_counter = self.epoch.data_ptr()
-        a.ws, a.ws_bytes = self.ws.data_ptr(), self.ws.numel()
-        a.status = self.status.data_ptr()
         a.ring = ring
         a.user_loc, a.user_scale = L.ptr(self.user_loc), L.ptr(self.user_scale)
-        self.args = a
+
+    write_hints = _SingleStepPlan.write_hints
 
     def destroy(self):
         if self.graph is not None:

@@ -270,13 +270,13 @@ class FilterResult(dict, Generic[TCorrection]):
         return tc
 
     # ---- writing ------------------------------------------------------------------------------------------------
-    def append(self, state: TCorrection, _ll_accumulated: bool = False):
+    def append(self, state: TCorrection, ll_added: bool = False):
         """One more state (result.py:119-133): its moments join the log, its log-likelihood the running total
-        (``_ll_accumulated``: the fused move that produced the state already added it - the total was its
+        (``ll_added``: the fused move that produced the state already added it - the total was its
         ``pf_filter_args.ll_total``)."""
         batched = self._loglikelihood.dim() > 0
         self._moments.append(state.get_mean(), state.get_variance(), batched)
-        if not _ll_accumulated:
+        if not ll_added:
             self._loglikelihood.add_(state.get_loglikelihood())
         self._states.append(state)
         return self

@@ -23,7 +23,7 @@ class RunHints:
         #                              for each other and a launch that cannot make progress REPORTS it (pf_filter_args.status)
         #                              instead of hanging: this package passes the status word with every such run, reads it
         #                              where it next waits for the device and re-issues the piece on the per-step route - same
-        #                              draws, same numbers (filters/particle/base.py: _verified_block, inference/smc2.py).  Runs on
+        #                              draws, same numbers (filters/particle/base.py: _reissue_per_step, inference/smc2.py).  Runs on
         #                              several streams / threads / processes of one device share the slots (pf_cluster.hpp)
         self.cluster_patience = 0    # pf_run_hints.cluster_patience (0 = the library's 2^21 polls; tests: -1 forces the give-up path)
         self.column_max_n = 0        # pf_run_hints.column_max_n (0 = the library's 2048)

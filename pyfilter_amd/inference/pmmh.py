@@ -5,6 +5,7 @@ accepted filters in with the column-move kernels.  Everything stays on the devic
 import torch
 from torch.distributions import Distribution, Independent, Normal
 
+from ..filters.particle import ParticleFilter
 from .utils import construct_mvn, theta_normalize
 
 
@@ -152,15 +153,13 @@ def _refilter(proposal_filter, y, stats):
     """The proposals' filters over the data.  A run on the column-cluster kernel reports through a status word when a launch could
     not make progress (its log-likelihoods are NaN then: the acceptance step rejects those proposals); verifying it here would
     make every move wait for its own re-filter, so the word goes to the caller (``stats["cluster_watch"]``), who reads it where
-    it next waits for the device - ``watch_refilters`` - and without a ``stats`` dictionary the run is verified on the spot."""
-    if stats is None or not hasattr(proposal_filter, "_cluster_gave_up"):
+    it next waits for the device - ``watch_refilters`` - and without a ``stats`` dictionary the run is verified on the spot, as is
+    the run of a filter that wraps ``batch_filter`` (it must be called through its wrapper).  ``stats["per_step"]``: this one run
+    takes the per-step route (the caller repeats a move whose cluster launch gave up)."""
+    if (stats is None or not isinstance(proposal_filter, ParticleFilter)
+            or type(proposal_filter).batch_filter is not ParticleFilter.batch_filter):
         return proposal_filter.batch_filter(y, bar=False)
-    proposal_filter._defer_status_once = True
-    try:
-        res = proposal_filter.batch_filter(y, bar=False)
-    finally:
-        proposal_filter._defer_status_once = False  # (a subclass that does not pass through ParticleFilter.batch_filter; an error)
-    watch = getattr(res, "_cluster_watch", None)
+    res, watch = proposal_filter._batch_filter(y, defer_status=True, per_step=stats.pop("per_step", False))
     if watch is not None:
         stats.setdefault("cluster_watch", []).append((watch[0], watch[1], proposal_filter))
     return res

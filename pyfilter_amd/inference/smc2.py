@@ -17,6 +17,7 @@ from typing import Callable, Optional
 import torch
 
 from ..distributed import Shard
+from ..filters.particle import ParticleFilter
 from ..filters.result import FilterResult
 from .parameters import ThetaParticles
 from .pmmh import SymmetricMH, as_draws, run_pmmh, watch_refilters
@@ -300,8 +301,8 @@ class ParticleMetropolisHastings:
             rate_now = float(rate)  # the kernel's one host decision per move
             if watch_refilters(stats):
                 # the move's re-filter ran on the column-cluster kernel and a launch gave up (its proposals were rejected, nothing
-                # else happened): the move again - the filter now re-issues on the per-step route itself (its plan was told)
-                proposal_filter._per_step_once = True
+                # else happened): the move again, its re-filter on the per-step route this once
+                stats["per_step"] = True
                 if rewind[0] is not None:
                     gen.set_state(rewind[0])  # the same proposals, the same acceptance uniforms ...
                 if rewind[1] is not None:
@@ -390,15 +391,11 @@ def online_move(alg, y: torch.Tensor, state: SMC2State):
             state.stats = stats[row]
             state.ess.append(state.stats[0])
             return ess, finite
-    watching = slot is not None and state._theta_step_applies() and hasattr(filt, "_online_cluster")
-    if watching:
-        filt._online_cluster = True
-    try:
-        filter_state = filt.filter(y, state.filter_state.latest_state, result=state.filter_state)
-    finally:
-        if watching:
-            filt._online_cluster = False
-    watched = getattr(filt, "_watched_move", None) if watching else None
+    if (slot is not None and state._theta_step_applies() and isinstance(filt, ParticleFilter)
+            and type(filt).filter is ParticleFilter.filter):
+        filter_state, watched = filt._filter_move(y, state.filter_state.latest_state, state.filter_state, watched=True)
+    else:  # (nobody reads a status word, or a subclass wraps filter() and must be called through it: an unwatched move)
+        filter_state, watched = filt.filter(y, state.filter_state.latest_state, result=state.filter_state), None
     if watched is None:
         ess, finite = slot.wait() if state.append(filter_state, slot) else state.stats.tolist()
     else:

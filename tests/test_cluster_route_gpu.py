@@ -437,16 +437,44 @@ def test_four_streams_of_cluster_launches_from_one_thread():
     for rep in range(3):
         for i, st in enumerate(streams):
             with torch.cuda.stream(st):
-                filters[i]._defer_status_once = True  # (no wait between the launches: the status words are read at the end)
-                outs[i].append(filters[i].batch_filter(y, bar=False))
+                outs[i].append(filters[i]._batch_filter(y, defer_status=True))  # (no wait between the launches: the status words are read at the end)
     torch.cuda.synchronize()
     for i in range(len(shapes)):
         assert getattr(filters[i], "cluster_fallbacks", 0) == 0
-        for r in outs[i]:
-            watch = getattr(r, "_cluster_watch", None)
+        for r, watch in outs[i]:
             assert watch is not None and int(watch[0].item()) == 0, "a launch gave up"
             assert torch.isfinite(r.loglikelihood).all()
-        assert torch.equal(outs[i][0].loglikelihood.cpu(), alone[i]), shapes[i]
+        assert torch.equal(outs[i][0][0].loglikelihood.cpu(), alone[i]), shapes[i]
+
+
+def test_an_online_move_after_a_block_on_the_same_plan_stays_on_the_per_step_route():
+    """``filter()`` -> ``filter_block()`` -> ``filter()`` on one filter of 2 052 particles (the smallest cluster size: three member
+    workgroups, the last holding four particles): the online move and the block share one plan and so one argument block.  The
+    block takes the cluster kernel (verified on the spot); the move after it is watched by nobody and must write its own hints
+    again - the per-step route - instead of running on the route the block's run left in those arguments."""
+    from pyfilter_amd import ops
+
+    g = torch.Generator().manual_seed(31)
+    y = (0.1 * torch.randn(5, generator=g)).cumsum(0).to(DEV)
+    f = _concurrent_filter(13, b=2, n=2052)
+
+    def spec():
+        torch.cuda.synchronize()
+        return ops.debug_launch_trace(1)[-1]["SPEC"]
+
+    state = f.initialize()
+    s1 = f.filter(y[0], state)
+    first = spec()
+    res, ll, _ = f.filter_block(y[1:4], s1)
+    block = spec()
+    s2 = f.filter(y[4], res.latest_state)
+    last = spec()
+    print("SPEC of the first move, the block, the last move:", first, block, last)
+    assert block == 10, "the block did not take the cluster kernel"
+    assert first != 10 and last != 10, (first, last)
+    assert torch.isfinite(s2.timeseries_state.value).all() and torch.isfinite(s2.weights).all()
+    assert torch.isfinite(s2.get_loglikelihood()).all()
+    assert f.cluster_fallbacks == 0
 
 
 def _process_worker(rank, barrier, out_dir, seed):
