@@ -181,6 +181,19 @@ int pf_sample_and_weight(const pf_model* model, int proposal, int weigh, const v
                          int64_t y_rows, const void* z, uint64_t seed, uint32_t step, void* x_out, void* w_out,
                          int64_t N, int64_t B, int dtype, void* stream);
 
+/* NestedProposal.sample_and_weight (proposals/nested.py:27-47) for a built-in model (every PF_HID_* of D, O <= 3 under either
+ * observation kind; PF_HID_LINEAR_MAT: PF_EUNSUPPORTED): per particle `num_samples` (1 .. PF_NESTED_MAX, else PF_EINVAL)
+ * candidates from the transition, x_out (D,B,N) the one kept with probability proportional to p(y | candidate), w_out (B,N) =
+ * log mean_j p(y | candidate_j) in the max-shifted form (finite where the reference's unshifted mean underflows; -inf when no
+ * candidate is valid - the pick is then min(floor(v M), M - 1)).  A candidate's NaN / +inf log-density counts as -inf.
+ * z (M,D,B,N) standard normals and v (B,N) uniforms in [0, 1) - the pick is the first j whose running sum of weights exceeds
+ * v * sum - or NULL -> Philox(seed, step): a run is a function of its seed.  pick_out (B,N), optional: the index kept.
+ * num_samples = 1 on the same z is pf_sample_and_weight(PF_PROP_BOOTSTRAP, weigh = 1). */
+#define PF_NESTED_MAX 256
+int pf_nested_sample_and_weight(const pf_model* model, int num_samples, const void* x, const void* y, int64_t y_rows,
+                                const void* z, const void* v, uint64_t seed, uint32_t step, void* x_out, void* w_out,
+                                int32_t* pick_out, int64_t N, int64_t B, int dtype, void* stream);
+
 /* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
  * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
 int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,

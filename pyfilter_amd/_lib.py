@@ -24,6 +24,7 @@ MAX_D = 3  # the fused / column / cluster kernels (PF_MAXD, PF_MAXO)
 MAX_O = 3
 LIN_MAX_D = 8  # PF_HID_LINEAR_MAT on the stand-alone model kernels (pf_linear.hpp)
 LIN_MAX_O = 8
+NESTED_MAX = 256  # PF_NESTED_MAX: candidates per particle pf_nested_sample_and_weight takes
 
 EXPORTS = (
     "pf_version", "pf_abi_version", "pf_error_string", "pf_workspace_bytes", "pf_normalize", "pf_systematic", "pf_systematic_cdf_free", "pf_systematic_logw",
@@ -32,7 +33,7 @@ EXPORTS = (
     "pf_filter_graph_destroy", "pf_columns_gather", "pf_columns_exchange", "pf_debug_draw_normals", "pf_debug_launch_trace",
     "pf_smooth_fixed_lag", "pf_smooth_ffbs", "pf_observed_flags", "pf_theta_ess", "pf_theta_fit", "pf_theta_propose",
     "pf_theta_accept", "pf_theta_path", "pf_theta_resample", "pf_initial_sample_cols", "pf_theta_step", "pf_host_alloc",
-    "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply",
+    "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply", "pf_nested_sample_and_weight",
 )
 
 
@@ -126,6 +127,7 @@ def load() -> C.CDLL:
     lib.pf_moments.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp, sz, vp]
     lib.pf_pre_weight.argtypes = [C.POINTER(PfModel), i32, vp, vp, i64, vp, i64, i64, i32, vp]
     lib.pf_sample_and_weight.argtypes = [C.POINTER(PfModel), i32, i32, vp, vp, i64, vp, u64, u32, vp, vp, i64, i64, i32, vp]
+    lib.pf_nested_sample_and_weight.argtypes = [C.POINTER(PfModel), i32, vp, vp, i64, vp, vp, u64, u32, vp, vp, vp, i64, i64, i32, vp]
     lib.pf_initial_sample.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u64, vp, i64, i64, i64, i32, vp]
     lib.pf_filter_run.argtypes = [C.POINTER(PfFilterArgs), i64, i64, i32, vp]
     lib.pf_filter_run_timed.argtypes = [C.POINTER(PfFilterArgs), i64, i64, i32, vp, C.POINTER(C.c_float)]

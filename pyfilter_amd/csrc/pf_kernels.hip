@@ -1584,6 +1584,31 @@ extern "C" int pf_sample_and_weight(const pf_model* model, int proposal, int wei
     });
 }
 
+// ---- the nested proposal (pf_nested.hpp) --------------------------------------------------------------------------------
+#include "pf_nested.hpp"
+extern "C" int pf_nested_sample_and_weight(const pf_model* model, int num_samples, const void* x, const void* y, int64_t y_rows,
+                                           const void* z, const void* v, uint64_t seed, uint32_t step, void* x_out, void* w_out,
+                                           int32_t* pick_out, int64_t N, int64_t B, int dtype, void* stream) {
+    int rc = check_model(model);
+    if (rc) return rc;
+    if (model->hid_kind == PF_HID_LINEAR_MAT) return PF_EUNSUPPORTED;  // (the callers' torch route)
+    if (!x || !y || !x_out || !w_out || bad_shape(N, B) || (y_rows != 1 && y_rows != B) || num_samples < 1 ||
+        num_samples > PF_NESTED_MAX)
+        return PF_EINVAL;
+    const ModelDesc md = to_desc(model);
+    const dim3 grid(ew_blocks(N), (int)B);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_d3(model->dim, [&](auto d) {
+            hipLaunchKernelGGL((k_nested_sample_and_weight<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
+                               num_samples, (const T*)x, (const T*)y, (int)y_rows, (const T*)z, (const T*)v, seed, step, (T*)x_out,
+                               (T*)w_out, pick_out, N, (int)B);
+            return launch_status();
+        });
+    });
+}
+
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;

@@ -1,5 +1,6 @@
 from .base import Proposal
 from .bootstrap import Bootstrap
 from .linear import LinearGaussianObservations
+from .nested import NestedProposal
 
-__all__ = ["Proposal", "Bootstrap", "LinearGaussianObservations"]
+__all__ = ["Proposal", "Bootstrap", "LinearGaussianObservations", "NestedProposal"]

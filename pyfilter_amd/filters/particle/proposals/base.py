@@ -84,10 +84,12 @@ class Proposal(ABC):
         new_x = x.propagate_from(values=ops.from_soa(x_out, c.batched, c.has_event))
         return new_x, (ops.from_cols(w_out, c.batched) if weigh else None)
 
-    def _kernel_pre_weight(self, y, x: TimeseriesState):
+    def _kernel_pre_weight(self, y, x: TimeseriesState, proposal: Optional[int] = None):
+        """``proposal``: the PF_PROP_* branch of ``pf_pre_weight`` (default: this class's own kernel proposal)."""
         c = self._ctx
         soa = ops.to_soa(x.value, c.batched, c.has_event)
-        return ops.from_cols(ops.pre_weight_soa(c.kind, c.params, self._KERNEL_PROPOSAL, soa, y), c.batched)
+        code = self._KERNEL_PROPOSAL if proposal is None else proposal
+        return ops.from_cols(ops.pre_weight_soa(c.kind, c.params, code, soa, y), c.batched)
 
     def _propagate(self, x: TimeseriesState) -> TimeseriesState:
         """``model.hidden.propagate`` (no weighting) for unobserved steps."""

@@ -11,7 +11,7 @@ ROUTE_AUTO, ROUTE_PER_STEP, ROUTE_COLUMN_GENERIC, ROUTE_CLUSTER, ROUTE_CLUSTER_A
 
 class RunHints:
     __slots__ = ("route", "column_max_n", "tile_target", "ancestor_search", "fused_step", "fused_batch", "graph", "direct",
-                 "theta_kernels", "cluster", "cluster_patience")
+                 "theta_kernels", "cluster", "cluster_patience", "nested_kernel")
 
     def __init__(self):
         self.reset()
@@ -33,6 +33,7 @@ class RunHints:
         self.fused_batch = True      # ``batch_filter()`` of a built-in model takes the fused run
         self.graph = True            # repeated fused runs of one configuration replay a captured hipGraph
         self.theta_kernels = True    # SMC^2 / PMMH moves and NESS updates of scalar standard-family priors: theta arithmetic in pf_theta_* / pf_jitter_* (else torch)
+        self.nested_kernel = True    # NestedProposal on a built-in model: pf_nested_sample_and_weight (else the torch route; tests compare the two)
         self.direct = False          # every plain fused run takes the direct driver (no persistent plan, no graph), not only single-launch runs
 
     def key(self):
@@ -64,7 +65,7 @@ class RunHints:
 
     def apply_mapping(self, m):
         """``PF_NO_COLUMN / PF_COLUMN_GENERIC / PF_CLUSTER (always) / PF_NO_CLUSTER / PF_COLUMN_MAX_N / PF_TARGET_WGS / PF_FORCE_SEARCH / PF_NO_FUSED_STEP /
-        PF_NO_FUSED_BATCH / PF_NO_GRAPH / PF_DIRECT / PF_NO_THETA_KERNELS`` of a mapping the CALLER owns -> attributes (absent keys: the defaults)."""
+        PF_NO_FUSED_BATCH / PF_NO_GRAPH / PF_DIRECT / PF_NO_THETA_KERNELS / PF_NO_NESTED_KERNEL`` of a mapping the CALLER owns -> attributes (absent keys: the defaults)."""
         on = lambda k: str(m.get(k, "0")) not in ("", "0")  # noqa: E731
         self.route = ROUTE_PER_STEP if on("PF_NO_COLUMN") else (ROUTE_COLUMN_GENERIC if on("PF_COLUMN_GENERIC") else
                                                                 (ROUTE_CLUSTER_ALWAYS if on("PF_CLUSTER") else ROUTE_AUTO))
@@ -75,6 +76,7 @@ class RunHints:
         self.fused_step, self.fused_batch, self.graph = not on("PF_NO_FUSED_STEP"), not on("PF_NO_FUSED_BATCH"), not on("PF_NO_GRAPH")
         self.direct = on("PF_DIRECT")
         self.theta_kernels = not on("PF_NO_THETA_KERNELS")
+        self.nested_kernel = not on("PF_NO_NESTED_KERNEL")
         self.cluster_patience = int(m.get("PF_CLUSTER_PATIENCE", 0) or 0)
         return self
 

@@ -334,6 +334,31 @@ def sample_and_weight_soa(kind, params, proposal: int, x: torch.Tensor, y: Optio
     return x_out, w_out
 
 
+def nested_sample_and_weight_soa(kind, params, m: int, x: torch.Tensor, y: torch.Tensor, z: Optional[torch.Tensor],
+                                 v: Optional[torch.Tensor], seed: int, step: int, want_pick: bool = False):
+    """NestedProposal.sample_and_weight on a built-in model (pf_nested_sample_and_weight): ``x (D, B, N)`` parents, ``m`` candidates
+    per particle from ``z (M, D, B, N)`` / ``v (B, N)`` or - ``None`` - from Philox(seed, step).  Returns (kept candidates
+    ``(D, B, N)``, log-weights ``(B, N)``, int32 picks ``(B, N)`` or None)."""
+    L.require_gpu(x, y, z, v, params)
+    d, b, n = x.shape
+    x_out = torch.empty_like(x)
+    w_out = torch.empty((b, n), dtype=x.dtype, device=x.device)
+    pick = torch.empty((b, n), dtype=torch.int32, device=x.device) if want_pick else None
+    yy, rows = _y_rows(y.to(x.dtype), b, kind.obs_dim)
+    if z is not None:
+        assert tuple(z.shape) == (m, d, b, n) and z.is_contiguous() and z.dtype == x.dtype
+    if v is not None:
+        assert tuple(v.shape) == (b, n) and v.is_contiguous() and v.dtype == x.dtype
+    assert x.is_contiguous()
+    mod = make_model_struct(kind, params)
+    L.check(
+        L.load().pf_nested_sample_and_weight(C.byref(mod), int(m), L.ptr(x), L.ptr(yy), rows, L.ptr(z), L.ptr(v), seed, step,
+                                             L.ptr(x_out), L.ptr(w_out), L.ptr(pick), n, b, L.dtype_code(x.dtype), L.stream_ptr()),
+        "pf_nested_sample_and_weight",
+    )
+    return x_out, w_out, pick
+
+
 def initial_sample_soa(m0, s0, n: int, b: int, d: int, dtype, device, seed: int, z: Optional[torch.Tensor] = None):
     x = torch.empty((d, b, n), dtype=dtype, device=device)
     L.require_gpu(x, z)
