@@ -194,6 +194,20 @@ int pf_nested_sample_and_weight(const pf_model* model, int num_samples, const vo
                                 const void* z, const void* v, uint64_t seed, uint32_t step, void* x_out, void* w_out,
                                 int32_t* pick_out, int64_t N, int64_t B, int dtype, void* stream);
 
+/* Forecasting from a filter state (what particle/state.py:173-174 `predict_path` is for): the weighted particles x (D,B,N),
+ * W (B,N) normalised weights (NULL: 1/N), walked `steps` moves of the hidden process ahead in ONE launch, with the predictive
+ * moments of every step: x_mean, x_var (steps,B,D) and y_mean, y_var (steps,B,O) in pf_moments' conventions (no division by
+ * sum W, variance clamped at 0).  The observation's moments use its conditional mean m(x) and scale s(x) - sum W m,
+ * sum W (m^2 + s^2) - so no observation noise enters them.  Optional (NULL: not written): x_path (steps,D,B,N) and
+ * y_path (steps,O,B,N) with y = m(x) + s(x) e.  z (steps,D,B,N) / e (steps,O,B,N): standard normals, or NULL -> Philox(seed),
+ * addressed by step and particle (the same x with or without paths; e is drawn only for y_path).
+ * Built-in kinds of D, O <= 3 only: steps < 1, a larger shape, PF_HID_LINEAR_MAT and PF_HID_USER_AFFINE are PF_EINVAL.
+ * ws: pf_forecast_workspace_bytes(N, B, steps) bytes (the tiles' partial sums, 104 B per step, filter and 1024 particles). */
+int pf_forecast_workspace_bytes(int64_t N, int64_t B, int steps, size_t* bytes);
+int pf_forecast(const pf_model* model, int steps, const void* x, const void* W, const void* z, const void* e, uint64_t seed,
+                void* x_mean, void* x_var, void* y_mean, void* y_var, void* x_path, void* y_path, void* ws, size_t ws_bytes,
+                int64_t N, int64_t B, int dtype, void* stream);
+
 /* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
  * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
 int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,

@@ -1609,6 +1609,40 @@ extern "C" int pf_nested_sample_and_weight(const pf_model* model, int num_sample
     });
 }
 
+// ---- forecasting (pf_forecast.hpp) ----------------------------------------------------------------------------------------
+#include "pf_forecast.hpp"
+static inline int64_t forecast_tiles(int64_t N) { return (N + PF_FC_TILE - 1) / PF_FC_TILE; }
+// the built-in kinds of the stand-alone model kernels with D, O <= 3; everything else is PF_EINVAL here (the callers' torch route)
+static inline bool forecast_takes(const pf_model* m) {
+    return m && m->params && m->hid_kind != PF_HID_LINEAR_MAT && m->hid_kind != PF_HID_USER_AFFINE && check_model(m) == PF_OK;
+}
+extern "C" int pf_forecast_workspace_bytes(int64_t N, int64_t B, int steps, size_t* bytes) {
+    if (!bytes || bad_shape(N, B) || steps < 1) return PF_EINVAL;
+    *bytes = sizeof(double) * (size_t)steps * PF_FC_Q * (size_t)B * (size_t)forecast_tiles(N);
+    return PF_OK;
+}
+extern "C" int pf_forecast(const pf_model* model, int steps, const void* x, const void* W, const void* z, const void* e, uint64_t seed,
+                           void* x_mean, void* x_var, void* y_mean, void* y_var, void* x_path, void* y_path, void* ws, size_t ws_bytes,
+                           int64_t N, int64_t B, int dtype, void* stream) {
+    if (!forecast_takes(model) || steps < 1 || !x || !x_mean || !x_var || !y_mean || !y_var || !ws || bad_shape(N, B)) return PF_EINVAL;
+    size_t need = 0;
+    pf_forecast_workspace_bytes(N, B, steps, &need);
+    if (ws_bytes < need) return PF_EWORKSPACE;
+    const ModelDesc md = to_desc(model);
+    const int tiles = (int)forecast_tiles(N);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_d3(model->dim, [&](auto d) {
+            hipLaunchKernelGGL((k_forecast_part<T, decltype(d)::value>), dim3(tiles, (int)B), dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
+                               steps, (const T*)x, (const T*)W, (const T*)z, (const T*)e, seed, (double*)ws, (T*)x_path, (T*)y_path, N, (int)B);
+            hipLaunchKernelGGL((k_forecast_final<T>), dim3(steps, (int)B), dim3(PF_BLOCK), 0, st, (const double*)ws, (T*)x_mean, (T*)x_var,
+                               (T*)y_mean, (T*)y_var, (int)model->dim, (int)model->obs_dim, (int)B, tiles);
+            return launch_status();
+        });
+    });
+}
+
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;

@@ -22,6 +22,7 @@ from ...timeseries.models import pack_params
 from ..base import BaseFilter
 from ..result import FilterResult
 from ..schedule import expand
+from .forecast import Forecast, kernel_applies, kernel_forecast, normalized_weights, torch_forecast
 from .proposals import Bootstrap, LinearGaussianObservations, Proposal
 from .proposals.base import KernelContext
 from .state import ParticleFilterCorrection, ParticleFilterPrediction
@@ -71,6 +72,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         self._draws = 0          # draw epoch: every new stream of random numbers (initial sample, fused run, online
                                  # move, step-by-step run) takes the next one - repeated calls are independent runs
         self._copies = 0
+        self._forecasts = 0      # forecast epoch: the seeds of ``forecast`` are its own - the run's draw epoch does not move
         self._obs_cache = None   # (identity of y, host copy of its observed flags): re-filtering the same data costs no sync
         self.cluster_fallbacks = 0  # column-cluster launches that gave up and were re-issued on the per-step route
         self._time_kernels, self.kernel_ms = False, None  # measurement knob: fused runs go through pf_filter_run_timed -> kernel_ms
@@ -230,6 +232,35 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
 
     def _propagate_only(self, prediction):
         return prediction.create_state_from_prediction(self._model, propagate=self._proposal._propagate)
+
+    def forecast(self, state, steps: int, paths: bool = False, z: Optional[torch.Tensor] = None, e: Optional[torch.Tensor] = None,
+                 seed: Optional[int] = None) -> Forecast:
+        """The predictive law ``steps`` moves of the hidden process ahead of ``state`` - a ``ParticleFilterCorrection`` or a
+        ``FilterResult`` (then its latest state): weighted predictive mean and variance of the state and of the observation at
+        every move, and with ``paths`` the particles' trajectories in ``predict_path``'s layout (``filters/particle/forecast.py``).
+        ``observe_every_step`` plays no part: a step is a move of the hidden process, as in ``sample_states``.
+
+        ``z (steps, N, [B], [D])`` / ``e (steps, N, [B], [O])``: the standard normals of the transitions / of the paths'
+        observation noise (parity mode).  Otherwise the draws are keyed by ``seed`` - by default derived from the filter's seed and
+        a forecast counter of its own.  Nothing of the filter's run changes: its draw counter, the state and its weights stay as
+        they are, so a run continued after a forecast is the run without one.
+
+        A built-in model of up to three state / observation components on a GPU takes one launch of ``pf_forecast``; anything
+        else the same computation as torch operations."""
+        if isinstance(state, FilterResult):
+            state = state.latest_state
+        steps = int(steps)
+        if steps < 1:
+            raise L.PfAmdError("forecast: steps must be at least 1")
+        if seed is None:
+            self._forecasts += 1
+            seed = (self._seed ^ (_GOLD * (self._forecasts + 0xF0CA57))) & _M64
+        x = state.timeseries_state
+        w = normalized_weights(state.weights)
+        ctx = self._ensure_context()
+        if kernel_applies(ctx, x.value):
+            return kernel_forecast(ctx, self._model.n_dim > 0, x, w, steps, paths, z, e, seed)
+        return torch_forecast(self._model, x, w, steps, paths, z, e, seed)
 
     def _copy_seed(self) -> int:
         """A copy draws its own random numbers (the reference's copies share torch's global generator, i.e. never repeat

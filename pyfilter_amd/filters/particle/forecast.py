@@ -1,0 +1,171 @@
+"""Forecasting from a filter state: the weighted particles walked ``steps`` moves of the hidden process ahead, with the predictive
+mean and variance of the state and of the observation at every one of them - what ``ParticleFilterCorrection.predict_path``
+(``particle/state.py:173-174``) is used for, with three differences: the particle weights enter, the
+observation's moments are Rao-Blackwellised (``sum W m(x)``, ``sum W (m(x)^2 + s(x)^2)`` from the observation density's
+conditional mean and scale: no observation noise is drawn for them), and the draws are the filter's own (Philox keyed by a seed,
+or tapes), not torch's global generator.
+
+* a built-in model of up to three state / observation components on a GPU: ``pf_forecast`` (``csrc/pf_forecast.hpp``) - one launch
+  for the whole horizon, nothing particle-sized written unless paths are asked for;
+* anything else (user callables, ``LinearModel``, a scalar state under a vector observation, CPU tensors): ``torch_forecast``, the
+  same outputs from the same tapes as torch operations.
+
+Moments follow ``get_filter_mean_and_variance``: weights are taken as normalised, the variance ``S2 - 2 mu S1 + mu^2 S0`` is
+clamped at 0."""
+from typing import Optional
+
+import torch
+from torch.distributions import Independent, Normal
+
+from ... import _lib as L
+from ... import ops
+from ...timeseries import AffineProcess, StateSpacePath, TimeseriesState
+
+
+class Forecast:
+    """``x_mean``, ``x_variance``: ``(steps, [B], [D])``; ``y_mean``, ``y_variance``: ``(steps, [B], [O])``; ``paths``: a
+    ``StateSpacePath`` in ``predict_path``'s layout - ``get_paths() -> (x (steps, N, [B], [D]), y (steps, N, [B], [O]))`` - or None."""
+
+    def __init__(self, x_mean, x_variance, y_mean, y_variance, paths: Optional[StateSpacePath] = None):
+        self.x_mean, self.x_variance, self.y_mean, self.y_variance, self.paths = x_mean, x_variance, y_mean, y_variance, paths
+
+    def __repr__(self):
+        return f"Forecast(steps: {self.x_mean.shape[0]}, x: {tuple(self.x_mean.shape[1:])}, y: {tuple(self.y_mean.shape[1:])}, " \
+               f"paths: {self.paths is not None})"
+
+
+def mix_forecasts(w: torch.Tensor, fc: Forecast) -> Forecast:
+    """The mixture of ``B`` filters' forecasts (moments ``(steps, B, ...)``) under the normalised weights ``w (B,)`` - the
+    posterior predictive of SMC2 / NESS: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + mean_b^2) - mean^2`` (clamped at
+    0).  Evaluated in float64, returned in the forecasts' type."""
+    def mix(mean, var):
+        m, v = mean.double(), var.double()
+        ww = w.to(device=m.device, dtype=torch.float64).reshape((1, -1) + (1,) * (m.dim() - 2))
+        mu = (ww * m).sum(1)
+        second = (ww * (v + m * m)).sum(1)
+        return mu.to(mean.dtype), (second - mu * mu).clamp_min(0.0).to(var.dtype)
+
+    xm, xv = mix(fc.x_mean, fc.x_variance)
+    ym, yv = mix(fc.y_mean, fc.y_variance)
+    return Forecast(xm, xv, ym, yv)
+
+
+def normalized_weights(log_w: torch.Tensor) -> torch.Tensor:
+    """``normalize`` of the log-weights ``(N, [B])`` WITHOUT its in-place sanitising of the argument (a forecast leaves the state
+    as it found it); on a CPU the same as torch operations (NaN, +inf and -inf count as the lowest finite value's weight)."""
+    if log_w.is_cuda:
+        from ...utils import normalize
+
+        return normalize(log_w.clone())
+    low = torch.finfo(log_w.dtype).min
+    lw = torch.nan_to_num(log_w, nan=low, posinf=low, neginf=low)
+    return torch.softmax(lw - lw.max(dim=0, keepdim=True)[0], dim=0)
+
+
+def kernel_applies(ctx, x: torch.Tensor) -> bool:
+    """A built-in kind of the stand-alone model kernels with ``D, O <= 3``, on a GPU."""
+    if ctx is None or not x.is_cuda:
+        return False
+    k = ctx.kind
+    return not k.is_user and k.hid_kind != L.HID_LINEAR_MAT and k.dim <= L.MAX_D and k.obs_dim is not None and k.obs_dim <= L.MAX_O
+
+
+def _tape_soa(t: Optional[torch.Tensor], like: torch.Tensor, batched: bool, has_event: bool) -> Optional[torch.Tensor]:
+    """``(steps, N, [B], [K])`` -> the kernel's ``(steps, K, B, N)``."""
+    if t is None:
+        return None
+    t = t.to(device=like.device, dtype=like.dtype)
+    if not has_event:
+        t = t.unsqueeze(-1)
+    if not batched:
+        t = t.unsqueeze(2)
+    return t.permute(0, 3, 2, 1).contiguous()
+
+
+def _path_view(p: torch.Tensor, batched: bool, has_event: bool) -> torch.Tensor:
+    """``(steps, K, B, N)`` -> the reference's ``(steps, N, [B], [K])`` view."""
+    v = p.permute(0, 3, 2, 1)
+    if not batched:
+        v = v[:, :, 0]
+    if not has_event:
+        v = v[..., 0]
+    return v
+
+
+def kernel_forecast(ctx, obs_event: bool, x: TimeseriesState, w: Optional[torch.Tensor], steps: int, paths: bool,
+                    z: Optional[torch.Tensor], e: Optional[torch.Tensor], seed: int) -> Forecast:
+    """``pf_forecast`` on the reference-layout state ``x`` and normalised weights ``w (N, [B])``."""
+    soa = ops.to_soa(x.value, ctx.batched, ctx.has_event)
+    xm, xv, ym, yv, xp, yp = ops.forecast_soa(ctx.kind, ctx.params, steps, soa, None if w is None else ops.to_cols(w),
+                                              _tape_soa(z, soa, ctx.batched, ctx.has_event), _tape_soa(e, soa, ctx.batched, obs_event),
+                                              seed, paths)
+
+    def shaped(m, event):
+        m = m if ctx.batched else m[:, 0]
+        return m if event else m[..., 0]
+
+    path = StateSpacePath.from_tensors(_path_view(xp, ctx.batched, ctx.has_event), _path_view(yp, ctx.batched, obs_event)) if paths else None
+    return Forecast(shaped(xm, ctx.has_event), shaped(xv, ctx.has_event), shaped(ym, obs_event), shaped(yv, obs_event), path)
+
+
+def _weighted(w: torch.Tensor, first: torch.Tensor, second: torch.Tensor, dtype):
+    """``(sum W first, sum W second - 2 mu sum W first + mu^2 sum W)`` over dim 0 in float64, the variance clamped at 0."""
+    ww = w.double().reshape(w.shape + (1,) * (first.dim() - w.dim()))
+    mu = (ww * first).sum(0)
+    var = (ww * second).sum(0) - 2.0 * mu * mu + mu * mu * ww.sum(0)
+    return mu.to(dtype), var.clamp_min(0.0).to(dtype)
+
+
+def _normal_base(dist) -> Optional[Normal]:
+    base = dist.base_dist if isinstance(dist, Independent) else dist
+    return base if isinstance(base, Normal) else None
+
+
+def torch_forecast(model, x: TimeseriesState, w: Optional[torch.Tensor], steps: int, paths: bool, z: Optional[torch.Tensor],
+                   e: Optional[torch.Tensor], seed: int) -> Forecast:
+    """The same forecast as torch operations on the model's callables, on the device of ``x``.  ``z (steps, N, [B], [D])`` /
+    ``e (steps, N, [B], [O])``: standard normals; without them the draws come from a ``torch.Generator`` seeded with ``seed``.
+    An affine process with Gaussian increments moves by ``loc + scale * (increment scale * z)``; any other process moves by its
+    own ``propagate`` (then a ``z`` tape is refused), and an observation density that is not Gaussian is sampled by its own
+    ``sample``."""
+    if steps < 1:
+        raise L.PfAmdError("forecast: steps must be at least 1")
+    hidden = model.hidden
+    value = x.value
+    dtype, device = value.dtype, value.device
+    lead = value.dim() - len(x.event_shape)
+    if w is None:
+        w = torch.full(value.shape[:lead], 1.0 / value.shape[0], dtype=torch.float64, device=device)
+    inc = getattr(hidden, "increment_distribution", None)
+    base = _normal_base(inc) if isinstance(hidden, AffineProcess) and inc is not None else None
+    kind = getattr(model, "kernel_kind", None)  # (its increment scale is a host double; the distribution's may be rounded)
+    # two generators - transitions, observation noise: the same seed moves the particles alike with or without paths
+    gen = torch.Generator(device=device).manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF) if z is None else None
+    gen_e = torch.Generator(device=device).manual_seed((int(seed) ^ 0x5DEECE66D) & 0x7FFFFFFFFFFFFFFF) if paths and e is None else None
+    rows = {k: [] for k in ("xm", "xv", "ym", "yv", "x", "y")}
+    for h in range(steps):
+        if base is not None:
+            zh = z[h].to(device=device, dtype=dtype) if z is not None else torch.randn(value.shape, generator=gen, dtype=dtype, device=device)
+            loc, scale = hidden.mean_scale(x)
+            x = x.propagate_from(values=loc + scale * (zh * kind.inc_scale if kind is not None and not kind.is_user else base.loc + base.scale * zh))
+        else:
+            if z is not None:
+                raise L.PfAmdError("a z tape needs an affine process with Gaussian increments")
+            x = hidden.propagate(x)
+        value = x.value
+        dens = model.build_density(x)
+        m, var = dens.mean, dens.variance
+        m, var = torch.broadcast_tensors(m, var)
+        xm, xv = _weighted(w, value.double(), value.double() ** 2, dtype)
+        ym, yv = _weighted(w, m.double(), m.double() ** 2 + var.double(), dtype)
+        for k, v in zip(("xm", "xv", "ym", "yv"), (xm, xv, ym, yv)):
+            rows[k].append(v)
+        if paths:
+            rows["x"].append(value)
+            if _normal_base(dens) is not None:
+                eh = e[h].to(device=device, dtype=dtype) if e is not None else torch.randn(m.shape, generator=gen_e, dtype=dtype, device=device)
+                rows["y"].append(m + dens.stddev * eh)
+            else:
+                rows["y"].append(dens.sample())
+    path = StateSpacePath(rows["x"], rows["y"]) if paths else None
+    return Forecast(*(torch.stack(rows[k], 0) for k in ("xm", "xv", "ym", "yv")), path)

@@ -19,7 +19,7 @@ from .. import _lib
 from ..hints import HINTS
 from .parameters import ThetaParticles
 from .pmmh import ThetaDraws, _to_device
-from .smc2 import SMC2State, online_move
+from .smc2 import SMC2State, online_move, posterior_forecast
 from .utils import theta_normalize, theta_systematic
 
 INFTY = math.inf
@@ -327,6 +327,11 @@ class BaseOnlineAlgorithm:
     def posterior_mean(self, state: SMC2State) -> torch.Tensor:
         """Weighted mean of the stacked (constrained) parameters over the theta-particles."""
         return theta_normalize(state.w) @ self.theta.stack_parameters(True)
+
+    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None):
+        """The posterior predictive ``steps`` moves ahead: the filters' forecasts mixed with the normalised theta-weights
+        (``smc2.posterior_forecast``)."""
+        return posterior_forecast(self.filter, state, steps, seed)
 
 
 class NESS(BaseOnlineAlgorithm):

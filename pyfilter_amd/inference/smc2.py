@@ -18,6 +18,7 @@ import torch
 
 from ..distributed import Shard
 from ..filters.particle import ParticleFilter
+from ..filters.particle.forecast import Forecast, mix_forecasts
 from ..filters.result import FilterResult
 from .parameters import ThetaParticles
 from .pmmh import SymmetricMH, as_draws, run_pmmh, watch_refilters
@@ -654,3 +655,18 @@ class SMC2:
         if self.shard.collective:
             vals, w = self.shard.all_gather(vals), self.shard.all_gather(w)
         return theta_normalize(w) @ vals
+
+    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None) -> Forecast:
+        """The posterior predictive ``steps`` moves ahead: the filters' forecasts (``ParticleFilter.forecast``) mixed with the
+        normalised theta-weights over ALL theta-particles (``mix_forecasts``)."""
+        return posterior_forecast(self.filter, state, steps, seed, self.shard)
+
+
+def posterior_forecast(filter_, state: SMC2State, steps: int, seed: Optional[int] = None, shard: Optional[Shard] = None) -> Forecast:
+    """``mix_forecasts`` of the forecasts of a state's filters under its theta-weights; on a collective shard the filters' moments
+    and the weights are all-gathered first, as ``posterior_mean`` gathers the parameters."""
+    fc, w = filter_.forecast(state.filter_state, steps, seed=seed), state.w
+    if shard is not None and shard.collective:
+        fc = Forecast(*(shard.all_gather(m, dim=1) for m in (fc.x_mean, fc.x_variance, fc.y_mean, fc.y_variance)))
+        w = shard.all_gather(w)
+    return mix_forecasts(theta_normalize(w), fc)

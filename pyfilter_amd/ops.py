@@ -359,6 +359,41 @@ def nested_sample_and_weight_soa(kind, params, m: int, x: torch.Tensor, y: torch
     return x_out, w_out, pick
 
 
+def forecast_soa(kind, params, steps: int, x: torch.Tensor, W: Optional[torch.Tensor], z: Optional[torch.Tensor] = None,
+                 e: Optional[torch.Tensor] = None, seed: int = 0, paths: bool = False):
+    """``steps`` moves of a built-in model's hidden process from the weighted particles ``x (D, B, N)``, ``W (B, N)`` normalised
+    weights (``None``: 1 / N), in one launch (pf_forecast): ``(x_mean, x_var (steps, B, D), y_mean, y_var (steps, B, O), x_path
+    (steps, D, B, N) | None, y_path (steps, O, B, N) | None)``.  ``z (steps, D, B, N)`` / ``e (steps, O, B, N)``: the standard
+    normals of the transitions / of the observation noise of the paths - ``None``: Philox(seed)."""
+    L.require_gpu(x, W, z, e, params)
+    d, b, n = x.shape
+    o, steps = int(kind.obs_dim), int(steps)
+    dt, dev = x.dtype, x.device
+    assert x.is_contiguous()
+    if W is not None:
+        assert tuple(W.shape) == (b, n) and W.is_contiguous() and W.dtype == dt
+    if z is not None:
+        assert tuple(z.shape) == (steps, d, b, n) and z.is_contiguous() and z.dtype == dt
+    if e is not None:
+        assert tuple(e.shape) == (steps, o, b, n) and e.is_contiguous() and e.dtype == dt
+    rows = max(steps, 0)
+    moments = [torch.empty((rows, b, k), dtype=dt, device=dev) for k in (d, d, o, o)]
+    x_path = torch.empty((rows, d, b, n), dtype=dt, device=dev) if paths else None
+    y_path = torch.empty((rows, o, b, n), dtype=dt, device=dev) if paths else None
+    nbytes = C.c_size_t(0)
+    if steps >= 1:  # (otherwise pf_forecast itself refuses the call)
+        L.check(L.load().pf_forecast_workspace_bytes(n, b, steps, C.byref(nbytes)), "pf_forecast_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=dev)
+    mod = make_model_struct(kind, params)
+    L.check(
+        L.load().pf_forecast(C.byref(mod), steps, L.ptr(x), L.ptr(W), L.ptr(z), L.ptr(e), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                             *[m.data_ptr() for m in moments], L.ptr(x_path), L.ptr(y_path), ws.data_ptr(), ws.numel(), n, b,
+                             L.dtype_code(dt), L.stream_ptr()),
+        "pf_forecast",
+    )
+    return (*moments, x_path, y_path)
+
+
 def initial_sample_soa(m0, s0, n: int, b: int, d: int, dtype, device, seed: int, z: Optional[torch.Tensor] = None):
     x = torch.empty((d, b, n), dtype=dtype, device=device)
     L.require_gpu(x, z)

@@ -240,6 +240,13 @@ class StateSpacePath:
     def __init__(self, xs, ys):
         self._x, self._y = torch.stack(xs, 0), torch.stack(ys, 0)
 
+    @classmethod
+    def from_tensors(cls, x: torch.Tensor, y: torch.Tensor) -> "StateSpacePath":
+        """Paths that already are ``(steps, *shape)`` tensors (views of a kernel's buffers): nothing is copied."""
+        path = cls.__new__(cls)
+        path._x, path._y = x, y
+        return path
+
     def get_paths(self):
         return self._x, self._y
 
