@@ -364,6 +364,7 @@ int pf_jitter_apply(const pf_theta_priors* priors, const void* values, const int
                                    * the exchange in its placement-independent form - agent-scope write-through stores and
                                    * L1-bypassing loads, never the same-XCD fast path: what a run falls back to whenever its
                                    * members do not share an XCD, pinned by the tests on every box */
+#define PF_ROUTE_PER_STEP_GENERIC 6 /* as PER_STEP, generic step kernels only: no launch takes the one-column leaf (tests, A/Bs) */
 typedef struct pf_run_hints {
     int32_t route;           /* PF_ROUTE_* */
     int32_t column_max_n;    /* largest filter the column-persistent kernel takes; 0 = the default (2048) */
@@ -529,6 +530,8 @@ int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_steps, void* 
  * out[i] = { step, sizeof(T), D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI } (10 int32 per record, the last 2048 are kept).
  * Returns the number of records written (>= 0) or a negative PF_E* code. */
 int pf_debug_launch_trace(int32_t* out, int max_records);
+/* The same with `fields` (1 .. 11) int32 per record: field 10 = the launch took the one-column leaf of the step kernel. */
+int pf_debug_launch_trace_fields(int32_t* out, int max_records, int fields);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,59 @@ template <typename T> struct FusedArgs {
                      // scans alone - log-weights would be overwritten unread: those stores are skipped (step_body, stage 4)
 };
 
+// The packed launch header of the one-column leaf (k_fused_step<..., ONECOL = true>: float scalar states, four particles per lane,
+// single-round tiles, inverted grid, closed-form model, APF steady state, B = 1 with an XCD tile map, no normal tape, no state
+// history, an interior state - filter_run_impl selects it per launch).  Every address a step workgroup needs, ready made on the
+// host: the kernel fetches it in ONE scalar clause at entry and waits once, the partials' loads depend on nothing else, and
+// the values behind its pointers (Philox epoch, offset, record, observations, pivot) form the second - and last - scalar level.
+// Passed by value AHEAD of FusedArgs, which the bookkeeper workgroup keeps using.  152 bytes: two 64-byte scalar loads and a tail
+// (the bound: three).  Measurements: DESIGN.md sections 3 and 5, profiles/onecol_leaf_*.txt.
+template <typename T> struct OneColHeader {
+    const double* pm2;         // incoming partials: the PQ_M2 row ...
+    const double* ps2;         // ... and the PQ_S2 row
+    double* part_out;          // the partials of state step + 1 (row stride = tiles)
+    const T* l_in;             // local scans of the incoming state / of state step + 1
+    T* l_out;
+    const T* x_in;             // particles of the incoming state / of state step + 1
+    T* x_out;
+    const uint64_t* seed_dev;  // FusedArgs::seed_dev (may be null)
+    uint64_t seed;
+    const T* cpack;            // the column's closed-form record (FastCol)
+    const T* y_t;              // &y[step]; y_{t+1} = y_t[y_rows]
+    const T* piv_mean;         // &means[step - 1]: the pivot of state step + 1's moments - null: the run's record *piv0
+    const double* piv0;
+    const T* u_t;              // &u_tape[step], or null: the offset is a Philox draw
+    int32_t* poison_cur;       // FusedArgs::poison slots of steps `step` and `step + 1`
+    int32_t* poison_next;
+    int N, tiles;              // (N <= 2^22 on this route: every index is 32 bits wide)
+    unsigned kmap;
+    int step;
+    T rcN;
+    int y_rows;
+};
+// What step_prologue / step_body take next to the argument block: nothing - or, ONECOL, the fetched header and its second level
+template <typename T, bool ONECOL> struct StepHeader {};
+template <typename T> struct StepHeader<T, true> {
+    OneColHeader<T> h;
+    uint64_t seed;     // h.seed + *h.seed_dev
+    T u;               // *h.u_t
+    T y_t, y_n;        // this step's and the next step's observation
+    T piv;             // pivot of the moments of state step + 1
+    T rec[PK_N];       // the closed-form record (the words FastCol::load reads)
+};
+// the step kernel's parameter: the argument block - the ONECOL leaf: behind its header
+template <typename T> struct OneColLaunch {
+    OneColHeader<T> h;
+    FusedArgs<T> a;
+};
+template <typename T> __device__ __forceinline__ const FusedArgs<T>& fused_args_of(const FusedArgs<T>& a) { return a; }
+template <typename T> __device__ __forceinline__ const FusedArgs<T>& fused_args_of(const OneColLaunch<T>& l) { return l.a; }
+template <typename T, bool ONECOL> struct StepKernArgs { using type = FusedArgs<T>; };
+template <typename T> struct StepKernArgs<T, true> { using type = OneColLaunch<T>; };
+// wants a scalar the kernel loads in an SGPR HERE: its load cannot sink to the first use behind a later branch (an input only -
+// the value stays what the compiler knows it to be, e.g. a pointer from the kernarg segment: global, not flat, accesses)
+template <typename V> __device__ __forceinline__ void pin_scalar(const V& v) { asm volatile("" ::"s"(v)); }
+
 // `late`: an opaque zero added to the row addresses (the step kernel ties it to a value computed after the ancestor
 // search, so the loads - and the registers they fill - cannot be hoisted above it)
 template <typename T, int D>
@@ -934,10 +987,13 @@ template <typename T> struct StepPlan {
 // Prologue of a step workgroup: the column's table from the partials of the incoming state, the resampling decision,
 // the window start (wave 0; broadcast through LDS).  Everything here is L2-hot and tiny: <= 16 KB of partials, one
 // 64-lane probe of the tile-local scans.
-template <typename T, int D, int VEC, int MODE, int SPEC, bool EARLY_Z, bool MULTI>
-__device__ __forceinline__ StepPlan<T> step_prologue(const FusedArgs<T>& a, const StepShared<T, D, VEC>& sh, T (&z0)[VEC][D]) {
+// ONECOL: `a` is the leaf's view of its header (k_fused_step: constants wherever the route fixes a value) and `hx` the header with
+// its second scalar level; the few places below that would otherwise derive an address from the argument block take it from there
+template <typename T, int D, int VEC, int MODE, int SPEC, bool EARLY_Z, bool MULTI, bool ONECOL = false>
+__device__ __forceinline__ StepPlan<T> step_prologue(const FusedArgs<T>& a, const StepShared<T, D, VEC>& sh, T (&z0)[VEC][D],
+                                                     const StepHeader<T, ONECOL>& hx = StepHeader<T, ONECOL>{}) {
     const Geom& g = a.g;
-    const int b = PF_STEP_B, k = a.tile_of_row(PF_STEP_K);
+    const int b = ONECOL ? 0 : PF_STEP_B, k = a.tile_of_row(PF_STEP_K);
     const int step = a.step;
     const bool obs = SPEC ? true : a.is_obs();
     const bool apf = SPEC ? (SPEC == 1) : (a.filter == PF_FILTER_APF);
@@ -951,7 +1007,9 @@ __device__ __forceinline__ StepPlan<T> step_prologue(const FusedArgs<T>& a, cons
     constexpr bool multinomial = MODE == 1;
     // issued first, used last: the Philox epoch / the step's systematic offset
     const uint64_t seed = a.seed + (a.seed_dev ? *a.seed_dev : 0ull);
-    const T u_taped = (!multinomial && a.u_tape) ? a.u_tape[(int64_t)step * g.B + b] : T(0);
+    T u_taped;
+    if constexpr (ONECOL) u_taped = hx.u;
+    else u_taped = (!multinomial && a.u_tape) ? a.u_tape[(int64_t)step * g.B + b] : T(0);
     const int64_t stride = (int64_t)g.B * g.tiles;
     const int64_t cb = (int64_t)b * g.tiles;
     double* const redm_d = sh.red + 2 * PF_NWAVES;
@@ -984,7 +1042,10 @@ __device__ __forceinline__ StepPlan<T> step_prologue(const FusedArgs<T>& a, cons
         q1 = two ? 0.0 : part[PQ_Q1 * stride + cb];
     }
     const bool few_tiles = SHORT && !one_tile && g.tiles <= PF_WAVE && a.debug_cut != 79;  // (uniform; 79: the general path)
-    if (!one_tile && !few_tiles) {
+    if constexpr (ONECOL) {
+        // (the header's two rows: "row 0" and "row 1" of a table whose stride is their distance)
+        load_col_partials<false, 0>(hx.h.pm2, (int64_t)(hx.h.ps2 - hx.h.pm2), 0, g.tiles, 0, 1, 0, p2);
+    } else if (!one_tile && !few_tiles) {
         if (two) load_col_partials<false, 0>(a.part_r(), stride, cb, g.tiles, PQ_M2, PQ_S2, 0, p2);
         else load_col_partials<true, 0>(a.part_r(), stride, cb, g.tiles, PQ_M1, PQ_S1, 0, p1);
     }
@@ -1124,9 +1185,9 @@ __device__ __forceinline__ StepPlan<T> step_prologue(const FusedArgs<T>& a, cons
 // scalar branch instructions (one set per particle and density) vanish (SQ_INSTS_SALU 1798 -> 962 per wave on
 // 64 x 65 536), 3 a user-defined affine process (PF_HID_USER_AFFINE: the one-step mean / scale of the PARENT come from the
 // caller's planes).  Closed-form kernels (FAST): the shape of the one-step mean, 0 run time, 1 affine, 2 sine.
-template <typename T, int D, int VEC, int MODE, int PROP, bool FAST, int SPEC, int MK, bool RS, bool MULTI>
+template <typename T, int D, int VEC, int MODE, int PROP, bool FAST, int SPEC, int MK, bool RS, bool MULTI, bool ONECOL = false>
 __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShared<T, D, VEC>& sh, const StepPlan<T>& pl,
-                                          const T (&z0)[VEC][D]) {
+                                          const T (&z0)[VEC][D], const StepHeader<T, ONECOL>& hx = StepHeader<T, ONECOL>{}) {
     const int proposal = (PROP >= 0) ? PROP : a.proposal;
     ModelDesc md = a.md;
     if constexpr (!FAST && MK == 1) { md.hid_kind = PF_HID_VERHULST_EM; md.obs_kind = PF_OBS_SV; md.obs_dim = 1; }
@@ -1151,7 +1212,7 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     T* const redm = sh.redm;
     int* hd = reinterpret_cast<int*>(win);  // systematic route: heads of the offspring ranges (the cdf window is not staged)
     const Geom& g = a.g;
-    const int b = PF_STEP_B, k = a.tile_of_row(PF_STEP_K);
+    const int b = ONECOL ? 0 : PF_STEP_B, k = a.tile_of_row(PF_STEP_K);
     const int tid = threadIdx.x;
     const int step = a.step;
     const int slot = step & 1;
@@ -1185,8 +1246,15 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     }
     const T ub = pl.ub;
 
-    const T* x_in = a.x[slot];
-    const T* lw_in = a.logw[slot] + (int64_t)b * g.N;
+    const T* x_in;   // (ONECOL: from the header - a run-time index into the view's arrays would keep the view in memory)
+    const T* lw_in;
+    if constexpr (ONECOL) {
+        x_in = hx.h.x_in;
+        lw_in = nullptr;  // (read by a step that carries its weights: never this one)
+    } else {
+        x_in = a.x[slot];
+        lw_in = a.logw[slot] + (int64_t)b * g.N;
+    }
 #ifdef PF_DEVTOOLS
     T* lw_out = a.logw[slot ^ 1] + (int64_t)b * g.N;
     int32_t* anc_col = a.anc + (int64_t)b * g.N;
@@ -1228,7 +1296,9 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     constexpr bool single = !MULTI;
     const bool use_lds = g.rounds_per_tile * PF_NWAVES <= PF_LDS_CHUNKS;
     double* const ct_tile = a.ctab_w(step + 1, b) + 2 * (int64_t)k * g.rounds_per_tile * PF_NWAVES;
-    T* const l_next = ((step & 1) ? a.cdf : a.pos) + (int64_t)b * g.N;  // the scans of state step + 1
+    T* l_next;  // the scans of state step + 1
+    if constexpr (ONECOL) l_next = hx.h.l_out;
+    else l_next = ((step & 1) ? a.cdf : a.pos) + (int64_t)b * g.N;
     int rk = 0;
     for (int r = 0; r < g.rounds_per_tile; ++r) {
         const int64_t r0 = base + (int64_t)r * g.round_elems;
@@ -1430,14 +1500,19 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
         // ---- 4. gather, propagate, weight -------------------------------------------------------------------------------
         // the column's constants are fetched only now - their address is tied to the ancestors by an opaque zero - so
         // they occupy registers for the arithmetic below and not across the search
-        int late;
-        asm volatile("v_readfirstlane_b32 %0, %1\n\ts_and_b32 %0, %0, 0" : "=s"(late) : "v"(idx[0]) : "scc");
+        // (ONECOL: none of this - the leaf's header and its second level were fetched at kernel entry)
+        int late = 0;
+        if constexpr (!ONECOL) asm volatile("v_readfirstlane_b32 %0, %1\n\ts_and_b32 %0, %0, 0" : "=s"(late) : "v"(idx[0]) : "scc");
         // the same for the output side of the argument block: re-read from the kernarg segment behind the opaque zero, so
         // the destination pointers are not held in (spilled) SGPRs through the prologue and the ancestor stage
         using KArgs = const __attribute__((address_space(4))) FusedArgs<T>;
         KArgs* la = (KArgs*)((const_ptr<char>)__builtin_amdgcn_kernarg_segment_ptr() + late);
-        T* const x_out = la->x[slot ^ 1];
-        if constexpr (FAST) {
+        T* x_out;
+        if constexpr (ONECOL) x_out = hx.h.x_out;
+        else x_out = la->x[slot ^ 1];
+        if constexpr (ONECOL) {
+            fc.load(&hx.rec[0], hx.y_t, hx.y_n);
+        } else if constexpr (FAST) {
             // scalar loads of the run's record (k_fused_reduce wrote it) and of this / the next step's observation
             const_ptr<T> yq = (const_ptr<T>)(uintptr_t)a.y + late;
             const int yc = a.y_rows == 1 ? 0 : b;
@@ -1537,7 +1612,8 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
             // unobserved step carries the weights and reads them, SISR keeps ancestors across its non-resampling steps: both
             // keep every store.  A plane that is not stored has its destination pointer not fetched either (flag and pointers
             // are fetched here, where they are used: they hold no SGPRs through the arithmetic above).
-            const bool keep = la->keep_state != 0;
+            bool keep = false;  // (ONECOL: an interior state by the route's rule)
+            if constexpr (!ONECOL) keep = la->keep_state != 0;
             const bool st_anc = keep || !apf;
             const bool st_lw = keep || !(apf && obs && pre_next);
 #pragma unroll
@@ -1568,9 +1644,13 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
             }
 #endif
             T piv[D];  // pivot of the moments of state step + 1: the mean of state step - 1, or the run's record (FusedArgs::pivot)
+            if constexpr (ONECOL) {
+                piv[0] = hx.piv;
+            } else {
 #pragma unroll
-            for (int d = 0; d < D; ++d)
-                piv[d] = (step - 1 >= a.t0) ? la->means[((int64_t)(step - 1) * g.B + b) * D + d] : (T)la->piv0[(int64_t)b * PF_MAXD + d];
+                for (int d = 0; d < D; ++d)
+                    piv[d] = (step - 1 >= a.t0) ? la->means[((int64_t)(step - 1) * g.B + b) * D + d] : (T)la->piv0[(int64_t)b * PF_MAXD + d];
+            }
             // the next resampling weights (scanned chunk by chunk below); the partial accumulator keeps the weights' own
             // family (moments, ll, ESS)
             if constexpr (MULTI) {
@@ -1597,7 +1677,11 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
         }
         if (windowed && r + 1 < g.rounds_per_tile) __syncthreads();  // the window is rewritten by the next round
     }
-    if (poison) atomicOr(&a.poison[(step & 3) * g.B + b], 1);
+    if constexpr (ONECOL) {
+        if (poison) atomicOr(hx.h.poison_cur, 1);
+    } else {
+        if (poison) atomicOr(&a.poison[(step & 3) * g.B + b], 1);
+    }
     if (PF_CUT(a, 3)) return;
     PF_STAMP(a, 14);
     T M1, M2, F1, F2;
@@ -1614,7 +1698,16 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     const int64_t i0s = base + tid * VEC;
     const bool on_s = i0s < g.N;
     double e[VEC], local = 0.0, incl = 0.0;
-    acc.template finish<MODE == 1>(a.part_w(step + 1), b, k, g.B, g.tiles, single && pre_next, red, redm, &a.poison[((step + 1) & 3) * g.B + b], M1, M2, F1, F2,
+    double* part_next;
+    int32_t* poison_next;
+    if constexpr (ONECOL) {
+        part_next = hx.h.part_out;
+        poison_next = hx.h.poison_next;
+    } else {
+        part_next = a.part_w(step + 1);
+        poison_next = &a.poison[((step + 1) & 3) * g.B + b];
+    }
+    acc.template finish<MODE == 1>(part_next, b, k, g.B, g.tiles, single && pre_next, red, redm, poison_next, M1, M2, F1, F2,
         [&](T f1, T f2) {
             if (!tile_scan) return;
             const T f = pre_next ? f2 : f1;
@@ -1678,8 +1771,11 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
 #endif
 }
 
-template <typename T, int D, int VEC, int MODE, int PROP, bool FAST, int SPEC, int MK, bool MULTI>
-__global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, MULTI>::value)) void k_fused_step(FusedArgs<T> a) {
+// ONECOL (OneColHeader): the leaf of the headline shape - the same stages on the same helpers in the same order, its results
+// bit-identical to the generic instantiation's; what it folds away is how a step workgroup gets at its operands.
+template <typename T, int D, int VEC, int MODE, int PROP, bool FAST, int SPEC, int MK, bool MULTI, bool ONECOL = false>
+__global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, MULTI>::value)) void k_fused_step(
+    typename StepKernArgs<T, ONECOL>::type ka) {
     using SH = StepShared<T, D, VEC>;
     __shared__ __attribute__((aligned(32))) T win[SH::WIN];
     __shared__ __attribute__((aligned(32))) T xwin[SH::XWIN ? D * SH::WIN : VEC];
@@ -1692,6 +1788,67 @@ __global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, 
     __shared__ int sh_plan[2];
     __shared__ double crec[MULTI ? 2 * PF_LDS_CHUNKS : 2];
     __shared__ double redb[PF_NWAVES];
+    if constexpr (ONECOL) {
+        static_assert(sizeof(T) == 4 && D == 1 && VEC == 4 && MODE == 0 && FAST && SPEC == 1 && !MULTI, "the one-column leaf's shape");
+        static_assert(sizeof(OneColHeader<T>) <= 192, "the header is fetched with three 64-byte scalar loads");
+        // ---- scalar level 1: the whole header, one clause, one wait ----
+        StepHeader<T, true> hx;
+        hx.h = ka.h;
+        OneColHeader<T>& h = hx.h;
+        pin_scalar(h.pm2); pin_scalar(h.ps2); pin_scalar(h.part_out); pin_scalar(h.l_in); pin_scalar(h.l_out); pin_scalar(h.x_in);
+        pin_scalar(h.x_out); pin_scalar(h.seed_dev); pin_scalar(h.seed); pin_scalar(h.cpack); pin_scalar(h.y_t); pin_scalar(h.piv_mean);
+        pin_scalar(h.piv0); pin_scalar(h.u_t); pin_scalar(h.poison_cur); pin_scalar(h.poison_next); pin_scalar(h.N); pin_scalar(h.tiles);
+        pin_scalar(h.kmap); pin_scalar(h.step); pin_scalar(h.rcN); pin_scalar(h.y_rows);
+        if (PF_STEP_K == (unsigned)h.tiles) {  // the bookkeeper (dispatched last: filter_run_impl), on the argument block as ever
+            column_bookkeeping<T, D>(ka.a, 0, red, redb);
+            return;
+        }
+        // ---- scalar level 2: what the header points at, issued together (the prologue waits for them once, behind its partials' loads) ----
+        // (no branch among the loads: an absent word is read from an address that is always valid - the record's - and dropped)
+        auto word = [](auto* p) { return (const_ptr<std::remove_cv_t<std::remove_pointer_t<decltype(p)>>>)(uintptr_t)p; };
+        const uint64_t epoch = *word(h.seed_dev ? h.seed_dev : (const uint64_t*)h.piv0);
+        const T u = *word(h.u_t ? h.u_t : h.cpack);
+        const T piv_m = *word(h.piv_mean ? h.piv_mean : h.cpack);
+        const double piv_r = *word(h.piv0);
+        hx.y_t = *word(h.y_t);
+        hx.y_n = word(h.y_t)[h.y_rows];
+#pragma unroll
+        for (int q = 0; q < PK_N; ++q) hx.rec[q] = word(h.cpack)[q];
+        {  // (ONE statement: the loads are issued back to back and waited for once)
+            const T(&c)[PK_N] = hx.rec;
+            asm volatile("" ::"s"(epoch), "s"(u), "s"(piv_m), "s"(piv_r), "s"(hx.y_t), "s"(hx.y_n), "s"(c[PK_A0]), "s"(c[PK_A1]),
+                         "s"(c[PK_A2]), "s"(c[PK_A3]), "s"(c[PK_G]), "s"(c[PK_INC]), "s"(c[PK_A]), "s"(c[PK_I2S]), "s"(c[PK_KS]),
+                         "s"(c[PK_CLOC]), "s"(c[PK_KSTD]), "s"(c[PK_INVG]), "s"(c[PK_I2INC]), "s"(c[PK_KT]), "s"(c[PK_KQ]),
+                         "s"(c[PK_I2C]), "s"(c[PK_KC]), "s"(c[PK_OB]), "s"(c[PK_OVI]), "s"(c[PK_COV]));
+        }
+        hx.seed = h.seed + (h.seed_dev ? epoch : 0ull);
+        hx.u = h.u_t ? u : T(0);
+        hx.piv = h.piv_mean ? piv_m : (T)piv_r;
+        // the step workgroups' view of the argument block: the header's values, and constants for everything the route fixes
+        FusedArgs<T> v{};
+        v.filter = PF_FILTER_APF;
+        v.g.N = (int64_t)(unsigned)h.N;
+        v.g.B = 1;
+        v.g.vec = VEC;
+        v.g.round_elems = v.g.tile_elems = PF_BLOCK * VEC;
+        v.g.rounds_per_tile = 1;
+        v.g.tiles = h.tiles;
+        v.rcN = h.rcN;
+        v.seed = hx.seed;  // (the epoch is folded in: seed_dev stays null)
+        v.cdf = v.pos = const_cast<T*>(h.l_in);
+        v.u_tape = h.u_t;  // (only ever tested: the value is hx.u)
+        v.step = h.step;
+        v.obs = v.obs_next = 1;
+        v.kmap = h.kmap;
+        const SH sh{win, xwin, &sh_j0, sh_cl, sh_wm, red, reds, redm, ptl, ftl, sh_plan, crec};
+        T z0[VEC][D];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) z0[j][0] = T(0);
+        const StepPlan<T> pl = step_prologue<T, D, VEC, MODE, SPEC, true, MULTI, true>(v, sh, z0, hx);
+        step_body<T, D, VEC, MODE, PROP, FAST, SPEC, MK, true, MULTI, true>(v, sh, pl, z0, hx);
+        return;
+    }
+    const FusedArgs<T>& a = fused_args_of(ka);
     // Grid (B, tiles + 1): x = the column, y = the tile - and y == tiles the column's bookkeeper (scratch: 2 + 2 D rows of `red`).
     // Workgroups are dispatched in linear order (x fastest), so every column's bookkeeper comes AFTER all step workgroups: see
     // filter_run_impl.  (The round-2 layout (tiles + 1, B) interleaved the bookkeepers with the columns: 2 - 3 us per step slower.)

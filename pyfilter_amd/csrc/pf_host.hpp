@@ -268,16 +268,18 @@ static inline ModelDesc to_desc(const pf_model* m) {
 // Test support: which step-kernel instantiation each launch of the calling thread's most recent fused runs selected
 // (pf_debug_launch_trace).  A per-thread ring, written on the host at launch time - nothing a kernel ever reads.
 #define PF_TRACE_LEN 2048
-#define PF_TRACE_FIELDS 10
+#define PF_TRACE_FIELDS 11
 struct LaunchTrace {
     int32_t rec[PF_TRACE_LEN][PF_TRACE_FIELDS];
     uint64_t count;
 };
 LaunchTrace& launch_trace();
-static inline void trace_launch(int step, int tbytes, int d, int vec, int mode, int prop, int fast, int spec, int mk, int multi) {
+// leaf: the launch took the one-column leaf of the step kernel (k_fused_step<..., ONECOL = true>) - the other fields say which one
+static inline void trace_launch(int step, int tbytes, int d, int vec, int mode, int prop, int fast, int spec, int mk, int multi, int leaf = 0) {
     LaunchTrace& t = launch_trace();
     int32_t* r = t.rec[t.count % PF_TRACE_LEN];
     r[0] = step; r[1] = tbytes; r[2] = d; r[3] = vec; r[4] = mode; r[5] = prop; r[6] = fast; r[7] = spec; r[8] = mk; r[9] = multi;
+    r[10] = leaf;
     ++t.count;
 }
 
@@ -334,6 +336,38 @@ static FusedArgs<T> make_fused_args(const pf_filter_args* A, const Geom& g, cons
     if (const char* dc = getenv("PF_DEBUG_CUT")) a.debug_cut = atoi(dc);
 #endif
     return a;
+}
+
+// The one-column leaf's launch header (OneColHeader) for the launch `a` describes: B = 1, so a column offset is zero and a row
+// of the partials is `tiles` long; every address is the one the generic kernel derives from the argument block for a.step
+template <typename T>
+static OneColHeader<T> make_onecol_header(const FusedArgs<T>& a) {
+    OneColHeader<T> h;
+    const int s = a.step;
+    const int64_t stride = (int64_t)a.g.tiles;
+    h.pm2 = a.part + (int64_t)(s & 1) * a.part_stride + PQ_M2 * stride;
+    h.ps2 = a.part + (int64_t)(s & 1) * a.part_stride + PQ_S2 * stride;
+    h.part_out = a.part + (int64_t)((s + 1) & 1) * a.part_stride;
+    h.l_in = (s & 1) ? a.pos : a.cdf;
+    h.l_out = (s & 1) ? a.cdf : a.pos;
+    h.x_in = a.x[s & 1];
+    h.x_out = a.x[(s & 1) ^ 1];
+    h.seed_dev = a.seed_dev;
+    h.seed = a.seed;
+    h.cpack = a.cpack;
+    h.y_t = a.y + (int64_t)s * a.y_rows;  // (scalar observations: check_model)
+    h.piv_mean = (s - 1 >= a.t0) ? a.means + (s - 1) : nullptr;
+    h.piv0 = a.piv0;
+    h.u_t = a.u_tape ? a.u_tape + s : nullptr;
+    h.poison_cur = a.poison + (s & 3);
+    h.poison_next = a.poison + ((s + 1) & 3);
+    h.N = (int)a.g.N;
+    h.tiles = a.g.tiles;
+    h.kmap = a.kmap;
+    h.step = s;
+    h.rcN = a.rcN;
+    h.y_rows = a.y_rows;
+    return h;
 }
 
 // A run's observed flags: the caller's host array (A->observed), the caller's device array (A->observed_dev), or - neither given -
@@ -486,7 +520,7 @@ static inline size_t column_lds_bytes(int64_t N, int D, size_t tsize, int vec) {
 // a column that fits one workgroup.  pf_run_hints.route = PF_ROUTE_PER_STEP keeps everything on the per-step route (tests compare the two).
 static inline bool column_eligible(const pf_filter_args* A, const Geom& g, int64_t n_steps, int finalize) {
     if (!finalize || n_steps < 1 || A->ring >= 3) return false;
-    if (A->hints.route == PF_ROUTE_PER_STEP) return false;
+    if (A->hints.route == PF_ROUTE_PER_STEP || A->hints.route == PF_ROUTE_PER_STEP_GENERIC) return false;
     const int64_t max_n = A->hints.column_max_n > 0 ? A->hints.column_max_n : PF_COLUMN_MAX_N;
     if (A->N > max_n || column_threads(A->N, PF_COLUMN_VEC) > 1024) return false;
     return column_lds_bytes(A->N, A->model.dim, A->dtype == PF_F64 ? 8 : 4, PF_COLUMN_VEC) <= 64 * 1024;  // (the default dynamic-LDS limit)

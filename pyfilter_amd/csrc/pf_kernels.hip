@@ -1944,15 +1944,17 @@ LaunchTrace& launch_trace() {
     static thread_local LaunchTrace t = {};
     return t;
 }
-extern "C" int pf_debug_launch_trace(int32_t* out, int max_records) {
-    if (!out || max_records < 0) return PF_EINVAL;
+extern "C" int pf_debug_launch_trace_fields(int32_t* out, int max_records, int fields) {
+    if (!out || max_records < 0 || fields < 1 || fields > PF_TRACE_FIELDS) return PF_EINVAL;
     const LaunchTrace& t = launch_trace();
     const uint64_t have = t.count < PF_TRACE_LEN ? t.count : PF_TRACE_LEN;
     const int n = (uint64_t)max_records < have ? max_records : (int)have;
     for (int i = 0; i < n; ++i)  // oldest of the last n first
-        for (int f = 0; f < PF_TRACE_FIELDS; ++f) out[i * PF_TRACE_FIELDS + f] = t.rec[(t.count - n + i) % PF_TRACE_LEN][f];
+        for (int f = 0; f < fields; ++f) out[i * fields + f] = t.rec[(t.count - n + i) % PF_TRACE_LEN][f];
     return n;
 }
+// (the record the ABI has documented since its first version: ten fields - callers size their buffers by it)
+extern "C" int pf_debug_launch_trace(int32_t* out, int max_records) { return pf_debug_launch_trace_fields(out, max_records, 10); }
 
 // theta: pf_filter_observe's theta update, which the cluster route folds into its launch (null: none)
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
@@ -2037,7 +2039,7 @@ extern "C" int pf_filter_graph_destroy(void* handle) {
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
                               float* kernel_ms, ThetaFold* theta) {
     if (!A || A->struct_size != sizeof(pf_filter_args)) return PF_EINVAL;  // (another ABI version: include/pf_amd.h)
-    if (A->hints.route < 0 || A->hints.route > PF_ROUTE_CLUSTER_SPREAD || A->hints.column_max_n < 0 || A->hints.tile_target < 0 ||
+    if (A->hints.route < 0 || A->hints.route > PF_ROUTE_PER_STEP_GENERIC || A->hints.column_max_n < 0 || A->hints.tile_target < 0 ||
         A->hints.cluster_patience < -1 || A->hints.cluster_patience > (1 << 30) || A->hints.cluster_generation < 0)
         return PF_EINVAL;
     int rc = check_model(&A->model, true);

@@ -282,7 +282,8 @@ template <typename T> __device__ __forceinline__ void write_col_pack(const Model
 template <typename T> struct FastCol {
     T A0, A1, A2, A3, g, inc, a, yb, ybn, i2s, ks, c_loc, c_y, kstd, inv_g, i2inc, kt, kq, i2c, kc;
     // y_t / y_next: this step's and the next step's observation (0 when there is none: the terms are then unused)
-    __device__ __forceinline__ void load(const_ptr<T> q, T y_t, T y_next) {
+    // (Q: a pointer to the record - const_ptr<T> for scalar loads, or a copy of it in registers)
+    template <typename Q> __device__ __forceinline__ void load(Q q, T y_t, T y_next) {
         A0 = q[PK_A0]; A1 = q[PK_A1]; A2 = q[PK_A2]; A3 = q[PK_A3];
         g = q[PK_G]; inc = q[PK_INC]; a = q[PK_A];
         i2s = q[PK_I2S]; ks = q[PK_KS]; c_loc = q[PK_CLOC]; kstd = q[PK_KSTD];

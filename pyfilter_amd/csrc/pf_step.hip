@@ -108,6 +108,19 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
             constexpr int SPEC = decltype(spec_c)::value;
             auto launch = [&](auto mk_c) {
                 constexpr int MK = decltype(mk_c)::value;
+                // The one-column leaf (OneColHeader): the APF steady state of ONE column of 2^q >= 16 single-round tiles on the
+                // closed-form kernels, writing an interior state - every address such a launch needs travels ready made in a
+                // packed header.  A normal tape, a state history (keep_state), flags the host does not know (SPEC), a batch, the
+                // run's last step: the generic kernel, as under PF_ROUTE_PER_STEP_GENERIC.
+                if constexpr (sizeof(T) == 4 && D == 1 && VEC == 4 && !MULTI && MODE == 0 && FAST && SPEC == 1 && (MK == 1 || MK == 2)) {
+                    if (A->hints.route != PF_ROUTE_PER_STEP_GENERIC && g.B == 1 && a.kmap != 0u && g.N <= ((int64_t)1 << 22) &&
+                        !a.z_tape && !ring && a.obs == 1 && a.obs_next == 1 && a.keep_state == 0 && !a.book_inline && a.debug_cut == 0) {
+                        trace_launch((int)a.step, (int)sizeof(T), D, VEC, MODE, PROP, 1, SPEC, MK, 0, 1);
+                        hipLaunchKernelGGL((k_fused_step<T, D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI, true>), grid, block, 0, st,
+                                           OneColLaunch<T>{make_onecol_header<T>(a), a});
+                        return;
+                    }
+                }
                 trace_launch((int)a.step, (int)sizeof(T), D, VEC, MODE, PROP, FAST ? 1 : 0, SPEC, MK, MULTI ? 1 : 0);
                 hipLaunchKernelGGL((k_fused_step<T, D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI>), grid, block, 0, st, a);
             };

@@ -15,7 +15,7 @@ import torch
 
 from ... import _lib as L
 from ... import ops
-from ...hints import HINTS, ROUTE_AUTO, ROUTE_CLUSTER, ROUTE_PER_STEP
+from ...hints import HINTS, ROUTE_AUTO, ROUTE_CLUSTER, ROUTE_PER_STEP, ROUTE_PER_STEP_GENERIC
 from ...resampling import multinomial, systematic
 from ...timeseries import AffineEulerMaruyama, StateSpaceModel, TimeseriesState
 from ...timeseries.models import pack_params
@@ -494,11 +494,13 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
     def batch_filter(self, y, bar=True, init_state=None) -> FilterResult:
         return self._batch_filter(y, init_state, bar=bar)[0]
 
-    def _batch_filter(self, y, init_state=None, *, bar=False, defer_status=False, per_step=False):
+    def _batch_filter(self, y, init_state=None, *, bar=False, defer_status=False, per_step=False, generic_steps=False):
         """``batch_filter`` with ``(result, watch)`` for callers inside this package.  ``defer_status`` (callers that never wait for a
         run by itself - PMMH moves): a run that took the column-cluster kernel is NOT verified before it is handed back; ``watch =
         (status word, plan)`` lets the caller look where it next waits for the device (a launch that gave up leaves NaN log-likelihoods:
-        a rejected proposal).  ``per_step``: a single-launch run takes the per-step route (the repeat of a run whose launch gave up)."""
+        a rejected proposal).  ``per_step``: a single-launch run takes the per-step route (the repeat of a run whose launch gave up).
+        ``generic_steps`` (tests, A/Bs): this run on the per-step route with the generic step kernels only - no launch takes the
+        one-column leaf (``PF_ROUTE_PER_STEP_GENERIC``); same draws, and bit for bit the same numbers."""
         assert self._model is not None, "Model has not been initialized!"
         device, _ = self._device_dtype()
         if (not self._fused_capable(device) or not isinstance(y, torch.Tensor)
@@ -507,8 +509,8 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             # (a user-defined affine process with recorded states: the driver's loop over fused single steps)
             return super().batch_filter(y, bar=bar, init_state=init_state), None
         if self._single_launch_run(y):
-            return self._batch_filter_lean(y, init_state, defer_status, per_step)
-        return self._batch_filter_fused(y, init_state), None
+            return self._batch_filter_lean(y, init_state, defer_status, per_step, generic_steps)
+        return self._batch_filter_fused(y, init_state, generic_steps=generic_steps), None
 
     def _single_launch_run(self, y) -> bool:
         """A run the library issues as ONE launch of the column-persistent kernel (filters of <= 2 048 particles) - or one or two
@@ -523,10 +525,11 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
                                             self._resampler_kind() == L.RESAMPLE_SYSTEMATIC))
                 and self._ctx_tapes_none())
 
-    def _batch_filter_lean(self, y: torch.Tensor, init_state, defer_status: bool, per_step: bool):
+    def _batch_filter_lean(self, y: torch.Tensor, init_state, defer_status: bool, per_step: bool, generic_steps: bool = False):
         state = init_state if init_state is not None else self.initialize()
         result = FilterResult(state, self.record_states, self.record_moments, _defer_moments=True)
-        blk, _, _ = self._filter_block_lean(y, state, None, None, host_u=True, defer_status=defer_status, per_step=per_step)
+        blk, _, _ = self._filter_block_lean(y, state, None, None, host_u=True, defer_status=defer_status, per_step=per_step,
+                                            generic_steps=generic_steps)
         result._extend_fused(blk.filter_means, blk.filter_variance, blk.loglikelihood, blk.latest_state)
         self._last_run["rows"] = (blk.filter_means, blk.filter_variance)
         return result, ((blk.status, blk.plan) if blk.status is not None else None)
@@ -650,7 +653,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         L.check(plan.run(plan.args_ref, t0, n_steps, 1, L.stream_ptr()), "pf_filter_run")
 
     def _filter_block_lean(self, y: torch.Tensor, state: ParticleFilterCorrection, observed, replay, host_u: bool = False,
-                           per_step: bool = False, defer_status: bool = False):
+                           per_step: bool = False, defer_status: bool = False, generic_steps: bool = False):
         """``filter_block`` for the caller it exists for - SMC^2, which issues a block of ~16 moves per host decision, a few
         dozen blocks per fit: at 1 000 theta x 400 particles such a block is 90 us of kernel time, and the general fused
         driver (persistent plan, staging copies in and out, a ``FilterResult`` with its moment log per call: ~25 small
@@ -704,7 +707,8 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         load_state()
         a = plan.args
         # (no key: an online move on this plan, i.e. this argument block, writes its own again.  ``per_step``: a re-issue after a give-up)
-        plan.write_hints(None, ROUTE_PER_STEP if per_step else None)
+        per_step = per_step or generic_steps  # (``generic_steps``: the per-step route without the one-column leaf)
+        plan.write_hints(None, ROUTE_PER_STEP_GENERIC if generic_steps else (ROUTE_PER_STEP if per_step else None))
         a.model.params = ctx.params.data_ptr()
         a.y, a.y_rows = y_dev.data_ptr(), rows
         a.observed, a.observed_dev = flags.data_ptr(), None
@@ -750,7 +754,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         res.plan = plan
         return res, ll_steps, (seed_eff, None)
 
-    def _batch_filter_fused(self, y: torch.Tensor, init_state=None, observed=None, replay=None) -> FilterResult:
+    def _batch_filter_fused(self, y: torch.Tensor, init_state=None, observed=None, replay=None, generic_steps: bool = False) -> FilterResult:
         state = init_state if init_state is not None else self.initialize()
         ctx = self._ensure_context()
         kind = ctx.kind
@@ -801,7 +805,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         use_graph = ((not taped) and not ring and replay is None and not self._time_kernels
                      and HINTS.graph and not kind.is_user and not self._move_by_move)
         key = (n, b, d, o, steps, rows, dtype, device, self._FILTER_KIND, self._proposal._KERNEL_PROPOSAL,
-               self._resampler_kind(), self._seed, float(self._resample_threshold), observed_host.numpy().tobytes(), HINTS.key())
+               self._resampler_kind(), self._seed, float(self._resample_threshold), observed_host.numpy().tobytes(), HINTS.key(), generic_steps)
         # a user-defined affine process that opted in (``graph_callable = True`` on the process): the run's whole launch sequence -
         # per move the callable's own torch launches and the library's kernel - is captured ONCE as a hipGraph (torch.cuda.graph)
         # and replayed: the callable's launches are a few microseconds of kernel each, issued eagerly they set the pace of a move
@@ -832,7 +836,8 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         word = (seed_eff - self._seed) & _M64
         plan.epoch.fill_(word - (1 << 64) if word >= (1 << 63) else word)
         a = plan.args
-        plan.write_hints(None)  # (a cached plan was keyed by them; a fresh one takes the current ones)
+        # (a cached plan was keyed by them; a fresh one takes the current ones.  ``generic_steps``: ``_batch_filter``)
+        plan.write_hints(None, ROUTE_PER_STEP_GENERIC if generic_steps else None)
         z_tape = u_tape = None
         if ctx.z_tape is not None:
             z_tape = ctx.z_tape[t_start:t_start + steps].contiguous()

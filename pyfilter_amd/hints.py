@@ -7,6 +7,7 @@ command line, the ``PF_*`` variables of a test driver's subprocess) - the packag
 The kernel-side choices travel to the library per call in ``pf_filter_args.hints`` (``include/pf_amd.h: pf_run_hints``)."""
 
 ROUTE_AUTO, ROUTE_PER_STEP, ROUTE_COLUMN_GENERIC, ROUTE_CLUSTER, ROUTE_CLUSTER_ALWAYS, ROUTE_CLUSTER_SPREAD = 0, 1, 2, 3, 4, 5
+ROUTE_PER_STEP_GENERIC = 6  # per call only (``_batch_filter(generic_steps=True)``): the per-step route without the one-column leaf
 
 
 class RunHints:

@@ -424,7 +424,7 @@ def initial_sample_cols(m0: torch.Tensor, s0: torch.Tensor, n: int, b: int, d: i
 SYNC_CHECKS = False  # True: index bounds of whole-filter moves are checked with a host round trip (an IndexError) instead
 # of torch's asynchronous device-side assert
 
-TRACE_FIELDS = ("step", "tbytes", "D", "VEC", "MODE", "PROP", "FAST", "SPEC", "MK", "MULTI")
+TRACE_FIELDS = ("step", "tbytes", "D", "VEC", "MODE", "PROP", "FAST", "SPEC", "MK", "MULTI", "LEAF")
 
 
 def debug_draw_normals(seed: int, steps: int, n: int, b: int, d: int, dtype, device, step0: int = 0) -> torch.Tensor:
@@ -441,11 +441,12 @@ TRACE_LEN = 2048  # launch records the library keeps per thread (PF_TRACE_LEN)
 
 
 def debug_launch_trace(last: int = 64):
-    """The step-kernel instantiations of this thread's latest fused launches, oldest first, as dicts (pf_debug_launch_trace)."""
+    """The step-kernel instantiations of this thread's latest fused launches, oldest first, as dicts (pf_debug_launch_trace_fields;
+    ``LEAF``: the launch took the one-column leaf of the step kernel)."""
     buf = (C.c_int32 * (len(TRACE_FIELDS) * last))()
-    n = L.load().pf_debug_launch_trace(buf, last)
+    n = L.load().pf_debug_launch_trace_fields(buf, last, len(TRACE_FIELDS))
     if n < 0:
-        L.check(n, "pf_debug_launch_trace")
+        L.check(n, "pf_debug_launch_trace_fields")
     k = len(TRACE_FIELDS)
     return [dict(zip(TRACE_FIELDS, buf[i * k:(i + 1) * k])) for i in range(n)]
 
