@@ -533,6 +533,13 @@ int pf_debug_launch_trace(int32_t* out, int max_records);
 /* The same with `fields` (1 .. 11) int32 per record: field 10 = the launch took the one-column leaf of the step kernel. */
 int pf_debug_launch_trace_fields(int32_t* out, int max_records, int fields);
 
+/* Residency of the one-column leaf of the step kernel (float scalar states, four particles per lane, APF steady state) for
+ * `proposal` (PF_PROP_*) and model kind `mk` (1: linear one-step mean, 2: sine diffusion) on the current device:
+ * *blocks_per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor at 256 threads and no dynamic LDS, *cus = its compute units.
+ * A column of 2^20 particles launches 1 024 step workgroups and one bookkeeper: they are all resident at once when
+ * *blocks_per_cu x *cus >= 1 025.  Returns PF_OK, PF_EINVAL for another (proposal, mk), or a positive HIP error code. */
+int pf_debug_leaf_residency(int proposal, int mk, int* blocks_per_cu, int* cus);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ EXPORTS = (
     "pf_multinomial", "pf_gather", "pf_loglik", "pf_moments", "pf_pre_weight", "pf_sample_and_weight",
     "pf_initial_sample", "pf_filter_run", "pf_filter_run_timed", "pf_filter_graph_create", "pf_filter_graph_launch",
     "pf_filter_graph_destroy", "pf_columns_gather", "pf_columns_exchange", "pf_debug_draw_normals", "pf_debug_launch_trace", "pf_debug_launch_trace_fields",
+    "pf_debug_leaf_residency",
     "pf_smooth_fixed_lag", "pf_smooth_ffbs", "pf_observed_flags", "pf_theta_ess", "pf_theta_fit", "pf_theta_propose",
     "pf_theta_accept", "pf_theta_path", "pf_theta_resample", "pf_initial_sample_cols", "pf_theta_step", "pf_host_alloc",
     "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply", "pf_nested_sample_and_weight",
@@ -158,6 +159,7 @@ def load() -> C.CDLL:
     lib.pf_debug_draw_normals.argtypes = [u64, u32, i64, vp, i64, i64, i64, i32, vp]
     lib.pf_debug_launch_trace.argtypes = [C.POINTER(C.c_int32), i32]
     lib.pf_debug_launch_trace_fields.argtypes = [C.POINTER(C.c_int32), i32, i32]
+    lib.pf_debug_leaf_residency.argtypes = [i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("pf_version", "pf_error_string"):

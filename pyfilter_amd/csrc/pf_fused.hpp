@@ -41,8 +41,15 @@ namespace pf {
             PF_STEP_B == 0 && threadIdx.x == 0)                                                 \
             (a).dbg[slot] = (unsigned long long)clock64();                                      \
     } while (0)
+// the bookkeeper workgroup of column 0 next to the eight sampled step workgroups (dbg[16 .. 31], step_prologue / step_body): its entry
+// and exit on the same wall clock, in two slots the cycle stamps leave free (dbg[6], dbg[7]; thread 0 is the one that writes the books)
+#define PF_BOOK_STAMP(a, b, slot)                                                               \
+    do {                                                                                        \
+        if ((a).debug_cut < 0 && (b) == 0 && threadIdx.x == 0) (a).dbg[slot] = wall_clock64();  \
+    } while (0)
 #else
 #define PF_CUT(a, n) false
+#define PF_BOOK_STAMP(a, b, slot) do { } while (0)
 #ifdef PF_ISA_MARKS  // stage boundaries as comments in the ISA listing (static instruction counts; they pin the schedule)
 #define PF_STAMP(a, slot) asm volatile("; PF_MARK " #slot)
 #else
@@ -945,6 +952,13 @@ __global__ __launch_bounds__(PF_BLOCK) void k_fused_book(FusedArgs<T> a) {
 // (profiles/r03_multinomial_scalar_waves.txt).  Single-round tiles stay at 4: 2^20 x 1 APF ran 20.4 -> 25.2 us at 3.
 #define PF_WAVES_D1_MN 3
 #define PF_WAVES_DN_A 3  // (4 waves = 128 VGPRs spill 128 B / lane once the prologue lives in this kernel: measured slower)
+// The one-column leaf (ONECOL): five workgroups per CU, so that a full-chip launch of 1 024 step workgroups (2^20 x 1) leaves
+// a resident slot for the column's bookkeeper - 256 CUs x 5 = 1 280 slots.  At four (1 024 slots) the bookkeeper, dispatched last,
+// entered when the first step workgroups retired and was the launch's last event.  Five waves per SIMD allow 96 VGPRs (512 / 5,
+// allocated in units of 8), five workgroups 32 768 B of LDS each (160 KiB per CU): see StepLds for the leaf's windows.
+// Measured: 11.76 -> 11.09 us per 2^20-particle step, most of it with the residency and not with the 76-register schedule
+// (profiles/leaf_residency_ab.txt); columns of 2^21 and 2^22 particles neither gain nor lose.
+#define PF_WAVES_LEAF 5
 // resident waves per SIMD the register allocation is tuned for (float; measured per variant, tools/kbench.py)
 template <typename T, int D, int MODE, int PROP, bool FAST, int SPEC, bool MULTI> struct StepWaves {
     static constexpr int value = sizeof(T) != 4 ? 1
@@ -975,6 +989,19 @@ template <typename T, int D, int VEC> struct StepShared {
     double* ftl;   // PF_MAX_TILES
     int* sh_plan;  // 2: window start of the tile's first position, its tile
     double* crec;  // 2 * PF_LDS_CHUNKS: raw chunk records (m_c, t_c) of the scan this launch writes
+};
+// Elements of the two windows the kernel declares.  Every instantiation but the leaf: the searching variants' power-of-two cdf
+// window (SearchWin::WIN) and the particles behind it, D planes of that stride.  The leaf (ONECOL: MODE 0, D = 1, one round per
+// tile) stages no cdf window and walks no plane stride, so it declares what MODE 0 touches: `win` is only ever `hd`, the heads of a
+// round's PF_BLOCK VEC positions plus one dump slot per lane (inverse_grid_heads); `xwin` is written and gathered below STAGED =
+// PF_BLOCK (VEC + V1) entries, V1 = 1 (step_body asserts both against its own constants).
+template <typename T, int D, int VEC, bool ONECOL> struct StepLds {
+    static constexpr int WIN = StepShared<T, D, VEC>::WIN;
+    static constexpr int XWIN = StepShared<T, D, VEC>::XWIN ? D * StepShared<T, D, VEC>::WIN : VEC;
+};
+template <typename T, int VEC> struct StepLds<T, 1, VEC, true> {
+    static constexpr int WIN = inverse_grid_heads(PF_BLOCK * VEC);
+    static constexpr int XWIN = PF_BLOCK * (VEC + 1);
 };
 // What the prologue hands to the body.
 template <typename T> struct StepPlan {
@@ -1202,6 +1229,12 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
     // the particles behind the cdf window are staged in LDS too when they are small (<= 8 B per particle), so the
     // ancestor gather is an LDS read instead of a second dependent global round trip
     constexpr bool XWIN = StepShared<T, D, VEC>::XWIN;
+    if constexpr (ONECOL) {  // the leaf's windows are sized by what this body touches (StepLds), not by the searching variants' WIN
+        static_assert(MODE == 0 && D == 1 && XWIN && sizeof(T) == sizeof(int), "the leaf's windows: heads in `win`, one plane in `xwin`");
+        static_assert(StepLds<T, D, VEC, true>::XWIN == STAGED, "xwin holds exactly the staged entries: in_lds gathers q < STAGED");
+        static_assert(StepLds<T, D, VEC, true>::WIN == inverse_grid_heads(PF_BLOCK * VEC) && StepLds<T, D, VEC, true>::WIN >= PF_BLOCK * VEC + PF_WAVE,
+                      "win holds the heads of a round of PF_BLOCK * VEC positions and inverse_grid_round's dump slots");
+    }
     T* const win = sh.win;
     T* const xwin = sh.xwin;
     int& sh_j0 = *sh.sh_j0;
@@ -1774,11 +1807,11 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
 // ONECOL (OneColHeader): the leaf of the headline shape - the same stages on the same helpers in the same order, its results
 // bit-identical to the generic instantiation's; what it folds away is how a step workgroup gets at its operands.
 template <typename T, int D, int VEC, int MODE, int PROP, bool FAST, int SPEC, int MK, bool MULTI, bool ONECOL = false>
-__global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, MULTI>::value)) void k_fused_step(
+__global__ __launch_bounds__(PF_BLOCK, (ONECOL ? PF_WAVES_LEAF : StepWaves<T, D, MODE, PROP, FAST, SPEC, MULTI>::value)) void k_fused_step(
     typename StepKernArgs<T, ONECOL>::type ka) {
     using SH = StepShared<T, D, VEC>;
-    __shared__ __attribute__((aligned(32))) T win[SH::WIN];
-    __shared__ __attribute__((aligned(32))) T xwin[SH::XWIN ? D * SH::WIN : VEC];
+    __shared__ __attribute__((aligned(32))) T win[StepLds<T, D, VEC, ONECOL>::WIN];
+    __shared__ __attribute__((aligned(32))) T xwin[StepLds<T, D, VEC, ONECOL>::XWIN];
     __shared__ int sh_j0;
     __shared__ int sh_cl[2 * PF_NWAVES], sh_wm[PF_NWAVES];
     __shared__ double red[(4 + 2 * D) * PF_NWAVES];
@@ -1800,7 +1833,9 @@ __global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, 
         pin_scalar(h.piv0); pin_scalar(h.u_t); pin_scalar(h.poison_cur); pin_scalar(h.poison_next); pin_scalar(h.N); pin_scalar(h.tiles);
         pin_scalar(h.kmap); pin_scalar(h.step); pin_scalar(h.rcN); pin_scalar(h.y_rows);
         if (PF_STEP_K == (unsigned)h.tiles) {  // the bookkeeper (dispatched last: filter_run_impl), on the argument block as ever
+            PF_BOOK_STAMP(ka.a, 0, 6);
             column_bookkeeping<T, D>(ka.a, 0, red, redb);
+            PF_BOOK_STAMP(ka.a, 0, 7);
             return;
         }
         // ---- scalar level 2: what the header points at, issued together (the prologue waits for them once, behind its partials' loads) ----
@@ -1840,6 +1875,10 @@ __global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, 
         v.step = h.step;
         v.obs = v.obs_next = 1;
         v.kmap = h.kmap;
+#ifdef PF_DEVTOOLS  // (the stamps of a leaf launch: PF_DEBUG_CUT < 0 - a stage cut never reaches the leaf, filter_run_impl)
+        v.debug_cut = ka.a.debug_cut;
+        v.dbg = ka.a.dbg;
+#endif
         const SH sh{win, xwin, &sh_j0, sh_cl, sh_wm, red, reds, redm, ptl, ftl, sh_plan, crec};
         T z0[VEC][D];
 #pragma unroll
@@ -1853,7 +1892,9 @@ __global__ __launch_bounds__(PF_BLOCK, (StepWaves<T, D, MODE, PROP, FAST, SPEC, 
     // Workgroups are dispatched in linear order (x fastest), so every column's bookkeeper comes AFTER all step workgroups: see
     // filter_run_impl.  (The round-2 layout (tiles + 1, B) interleaved the bookkeepers with the columns: 2 - 3 us per step slower.)
     if (!a.book_inline && PF_STEP_K == (unsigned)a.g.tiles) {
+        PF_BOOK_STAMP(a, PF_STEP_B, 6);
         column_bookkeeping<T, D>(a, PF_STEP_B, red, redb);
+        PF_BOOK_STAMP(a, PF_STEP_B, 7);
         return;
     }
     const SH sh{win, xwin, &sh_j0, sh_cl, sh_wm, red, reds, redm, ptl, ftl, sh_plan, crec};

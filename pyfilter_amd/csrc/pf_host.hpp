@@ -493,6 +493,10 @@ template <typename T, int D, int VEC, bool MULTI>
 int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, int64_t t0, int64_t n_steps, int finalize,
                     hipStream_t st, float* kernel_ms);
 
+// (test support, pf_debug_leaf_residency: resident workgroups per CU of the one-column leaf k_fused_step<float, 1, 4, 0, proposal, true,
+// 1, mk, false, true> at PF_BLOCK threads and no dynamic LDS, and the device's CU count - defined by the object that owns the leaf)
+int leaf_residency(int proposal, int mk, int* blocks_per_cu, int* cus);
+
 // ---- the column-persistent route (pf_column.hpp): filters of a few hundred .. a few thousand particles -----------------
 // One launch per run (per PFC_OBS_WORDS * 32 steps): no reduce / bookkeeping launches, no per-column records.
 static inline int column_threads(int64_t N, int vec) {

@@ -1956,6 +1956,11 @@ extern "C" int pf_debug_launch_trace_fields(int32_t* out, int max_records, int f
 // (the record the ABI has documented since its first version: ten fields - callers size their buffers by it)
 extern "C" int pf_debug_launch_trace(int32_t* out, int max_records) { return pf_debug_launch_trace_fields(out, max_records, 10); }
 
+extern "C" int pf_debug_leaf_residency(int proposal, int mk, int* blocks_per_cu, int* cus) {
+    if (!blocks_per_cu || !cus) return PF_EINVAL;
+    return leaf_residency(proposal, mk, blocks_per_cu, cus);
+}
+
 // theta: pf_filter_observe's theta update, which the cluster route folds into its launch (null: none)
 static int filter_run_checked(const pf_filter_args* A, int64_t t0, int64_t n_steps, int finalize, void* stream,
                               float* kernel_ms, ThetaFold* theta);

@@ -86,6 +86,8 @@ __device__ __forceinline__ void grid_counts_local(const T (&c)[VEC], T u, T nT, 
 // window does not reach (from = first index not staged, or 0 when - defensively - no head precedes the position).
 // sh_cl: 2 * PF_NWAVES ints, sh_wm: PF_NWAVES ints.  Three barriers.
 #define PF_MAX_WINDOWS 12
+// ints `hd` must hold for a round of RE positions: the RE heads and one dump slot per lane behind them (`dump = RE + lane` below)
+constexpr int inverse_grid_heads(int round_elems) { return round_elems + PF_WAVE; }
 // `next_window(it, d0, d1)` stages the cdf entries [ws + it * S, ws + (it + 1) * S) the same way (returns false when
 // the column ends before them).  It is only called when the windows so far do not account for all RE positions - a
 // stretch of negligible weights - and lets the workgroup walk on window by window (up to PF_MAX_WINDOWS) before the

@@ -43,9 +43,11 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
 #ifdef PF_DEVTOOLS
     if (const char* bi = getenv("PF_BOOK_INLINE")) a.book_inline = atoi(bi);  // (2: nobody keeps the books - timing experiments)
 #endif
-    // Grid (B, tiles + 1), x = the column: blocks are dispatched in linear order and a 2^20-particle step fills every
-    // resident slot of the chip (1 024 = 4 per CU: 33 KB of LDS, 113 VGPRs) - with the tile index slowest the bookkeepers
-    // (y == tiles) come after ALL step workgroups and fill slots as they free up; as block (tiles, b) of a (tiles + 1, B) grid
+    // Grid (B, tiles + 1), x = the column: blocks are dispatched in linear order and a 2^20-particle step of the generic kernel
+    // fills every resident slot of the chip (1 024 = 4 per CU: 33 KB of LDS, 97 - 128 VGPRs) - with the tile index slowest the
+    // bookkeepers (y == tiles) come after ALL step workgroups and fill slots as they free up.  For ONE column that means: the
+    // bookkeeper starts when the first step workgroup retires and runs on alone - which is why the one-column leaf is built for
+    // 5 per CU (1 280 slots: PF_WAVES_LEAF, StepLds) and its bookkeeper starts with the step workgroups.  As block (tiles, b) of a (tiles + 1, B) grid
     // they sat between the columns, took slots first, and the last columns' step workgroups started 2 - 3 us late
     // (profiles/r04c_step_kernel_bookkeepers_last_ab.txt).  B = 1 is the same linear order either way.
     a.kmap = 0u;
@@ -114,7 +116,7 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
                 // run's last step: the generic kernel, as under PF_ROUTE_PER_STEP_GENERIC.
                 if constexpr (sizeof(T) == 4 && D == 1 && VEC == 4 && !MULTI && MODE == 0 && FAST && SPEC == 1 && (MK == 1 || MK == 2)) {
                     if (A->hints.route != PF_ROUTE_PER_STEP_GENERIC && g.B == 1 && a.kmap != 0u && g.N <= ((int64_t)1 << 22) &&
-                        !a.z_tape && !ring && a.obs == 1 && a.obs_next == 1 && a.keep_state == 0 && !a.book_inline && a.debug_cut == 0) {
+                        !a.z_tape && !ring && a.obs == 1 && a.obs_next == 1 && a.keep_state == 0 && !a.book_inline && a.debug_cut <= 0) {  // (< 0: stamps only, development build)
                         trace_launch((int)a.step, (int)sizeof(T), D, VEC, MODE, PROP, 1, SPEC, MK, 0, 1);
                         hipLaunchKernelGGL((k_fused_step<T, D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI, true>), grid, block, 0, st,
                                            OneColLaunch<T>{make_onecol_header<T>(a), a});
@@ -190,12 +192,13 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
         // prepare_next say.  The step kernel skips the stores of an interior state's planes that would be overwritten unread.
         a.keep_state = (ring != 0 || s + 1 == n_steps) ? 1 : 0;
 #ifdef PF_DEVTOOLS
-        if (a.debug_cut != 0) a.keep_state = 1;  // (the stage cuts 2 / 4 / 5 write through lw_out / anc_col)
+        if (a.debug_cut > 0) a.keep_state = 1;  // (the stage cuts 2 / 4 / 5 write through lw_out / anc_col)
         // stage cuts on ONE launch (the last but one step) when PF_DEBUG_CUT_AT_END is set: the state entering it is
-        // valid, so per-dispatch PMC rows of that launch profile the stages on real data
+        // valid, so per-dispatch PMC rows of that launch profile the stages on real data.  The stamps (PF_DEBUG_CUT < 0) likewise: every
+        // stamping launch overwrites the one before, and a run's LAST launch writes a kept state - it is never the one-column leaf
         static const bool cut_at_end = getenv("PF_DEBUG_CUT_AT_END") != nullptr;
         const int cut_all = a.debug_cut;
-        if (cut_at_end && cut_all > 0 && s != n_steps - 2) a.debug_cut = 0;
+        if (cut_at_end && cut_all != 0 && s != n_steps - 2) a.debug_cut = 0;
 #endif
         launch_step();
 #ifdef PF_DEVTOOLS
@@ -213,6 +216,25 @@ int filter_run_impl(const pf_filter_args* A, const Geom& g, const WsLayout& wl, 
     if (const int rc = timer.finish(n_steps)) return rc;
     return launch_status();
 }
+
+#if PF_STEP_SET == PF_STEP_KERNELS_f32d1_v4 && PF_STEP_MULTI == 0
+// pf_debug_leaf_residency (pf_kernels.hip): what the runtime says about the one-column leaf's instantiations, which this object owns
+int leaf_residency(int proposal, int mk, int* blocks_per_cu, int* cus) {
+    if ((proposal != PF_PROP_BOOTSTRAP && proposal != PF_PROP_LGO) || (mk != 1 && mk != 2)) return PF_EINVAL;
+    auto ask = [&](auto prop_c, auto mk_c) -> int {
+        int dev = 0;
+        if (const hipError_t e = hipGetDevice(&dev)) return (int)e;
+        if (const hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev)) return (int)e;
+        return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            blocks_per_cu, k_fused_step<float, 1, 4, 0, decltype(prop_c)::value, true, 1, decltype(mk_c)::value, false, true>, PF_BLOCK, 0);
+    };
+    auto with_mk = [&](auto prop_c) {
+        return mk == 1 ? ask(prop_c, std::integral_constant<int, 1>{}) : ask(prop_c, std::integral_constant<int, 2>{});
+    };
+    return proposal == PF_PROP_BOOTSTRAP ? with_mk(std::integral_constant<int, PF_PROP_BOOTSTRAP>{})
+                                         : with_mk(std::integral_constant<int, PF_PROP_LGO>{});
+}
+#endif
 
 // explicit instantiations: the leaves this object owns
 #define PF_LEAF_AT(T, D, VEC, MULTI) \

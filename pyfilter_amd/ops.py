@@ -451,6 +451,15 @@ def debug_launch_trace(last: int = 64):
     return [dict(zip(TRACE_FIELDS, buf[i * k:(i + 1) * k])) for i in range(n)]
 
 
+def debug_leaf_residency(proposal: int, mk: int):
+    """``(blocks_per_cu, cus)`` of the one-column leaf of the step kernel for ``proposal`` (``_lib.PROP_*``) and model kind ``mk`` (1, 2)
+    on the current device: the runtime's resident workgroups per compute unit at 256 threads, and the compute units
+    (pf_debug_leaf_residency)."""
+    blocks, cus = C.c_int(0), C.c_int(0)
+    L.check(L.load().pf_debug_leaf_residency(proposal, mk, C.byref(blocks), C.byref(cus)), "pf_debug_leaf_residency")
+    return blocks.value, cus.value
+
+
 def observed_flags(y: torch.Tensor) -> torch.Tensor:
     """``y (T, ...)`` -> ``(T,)`` uint8 on the device: 1 unless the whole observation is NaN (pf_observed_flags;
     ``filters/base.py:212``)."""

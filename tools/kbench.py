@@ -161,6 +161,8 @@ def main():
             t0w = min(st[16:24])
             print("   wall clock (10 ns ticks since the first of 8 sampled workgroups, tiles 0,128,..,896): start", [v - t0w for v in st[16:24]],
                   " end", [v - t0w for v in st[24:32]])
+            print("   bookkeeper workgroup of column 0 on the same clock: entry", st[6] - t0w, " exit", st[7] - t0w,
+                  " (earliest sampled step-workgroup exit", min(st[24:32]) - t0w, ", latest", max(st[24:32]) - t0w, ")")
             print("   stamps of workgroup", -int(os.environ["PF_DEBUG_CUT"]) - 1, "(clock64 ticks from kernel entry: table built, window start known | body entry, "
                   "pre-loop, loads issued + normals, ancestors, compute + stores, push, pre-finish, end):", sp)
         print(f"{name:22s} us/step {1e6 * wall / T:8.2f}  particle-steps/s {n * b * T / wall:10.3e}  kernels(us, event-bracketed) "

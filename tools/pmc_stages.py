@@ -41,14 +41,17 @@ def collect(config, counters, cut, kernel="k_fused_step"):
 
 
 def build_dev():
-    """libpfamd_dev.so: the float / scalar-state / VEC = 4 step units rebuilt with -DPF_DEVTOOLS (cycle stamps + stage cuts compiled
-    in), linked with the production objects of all other units (tools/build_some.py; build/obj, from __graft_entry__.build())."""
+    """libpfamd_dev.so: the main unit (pf_debug_offset: where the workspace keeps the stamps) and the float / scalar-state / VEC = 4 step
+    units rebuilt with -DPF_DEVTOOLS (cycle stamps, the bookkeeper's and the sampled step workgroups' wall-clock stamps + stage cuts
+    compiled in), linked with the production objects of all other units (tools/build_some.py; build/obj, from __graft_entry__.build()).
+    The stamps are printed by tools/kbench.py under PF_DEBUG_CUT=-<workgroup + 1> (PF_DEBUG_CUT_AT_END=1: those of the run's last-but-one
+    launch alone - at 2^20 x 1 a launch of the one-column leaf)."""
     from build_some import rebuild
 
     out = os.path.join(ROOT, "pyfilter_amd", "libpfamd_dev.so")
     csrc = os.path.join(ROOT, "pyfilter_amd", "csrc")
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc)):
-        out = rebuild(["f32d1_v4_m0", "f32d1_v4_m1"], ["-DPF_DEVTOOLS"], "dev")
+        out = rebuild(["main", "f32d1_v4_m0", "f32d1_v4_m1"], ["-DPF_DEVTOOLS"], "dev")
     return out
 
 
