@@ -388,20 +388,39 @@ def ffbs_logits(spec, x_t, w_t, x_next):
     return w_t.unsqueeze(0) + lp
 
 
+def ffbs_sanitize_logw(w):
+    """The log-weights of a recorded state as a backward draw takes them: NaN, ``+inf`` and the dtype's lowest finite value
+    (what ``normalize``'s ``nan_to_num_`` leaves of a ``-inf``) are ``-inf`` - a candidate without mass.  A copy; idempotent."""
+    bad = w.isnan() | (w == math.inf) | (w <= torch.finfo(w.dtype).min)
+    return w.masked_fill(bad, -math.inf)
+
+
+def ffbs_backward_step(spec, x_t, w_t, x_next, u_t):
+    """One backward draw of ``_do_sample_ffbs`` (particle/base.py:112-122) by inverse CDF: trajectory j at ``x_next (N_j,[B],[D])``
+    takes the first candidate i of state t ``(x_t (N_i,[B],[D]), w_t (N_i,[B]))`` whose running sum of ``exp(logit - max)`` exceeds
+    ``u_t[j] * total`` - and, when none does (``u`` within rounding of 1), the last candidate of positive mass.  Max and exp in
+    the inputs' dtype, the running sum in float64.  Returns ``(idx (N_j,[B]) int64, cdf_norm (N_j,[B],N_i) float64)``, the cdf
+    divided by its last entry."""
+    logits = ffbs_logits(spec, x_t, ffbs_sanitize_logw(w_t), x_next)  # (N_j, N_i, [B])
+    if logits.dim() == 3:
+        logits = logits.moveaxis(1, 2)  # (N_j, B, N_i)
+    m = logits.max(dim=-1, keepdim=True)[0]
+    e = (logits - m).exp().double()
+    cdf = e.cumsum(dim=-1)
+    total = cdf[..., -1:]
+    beyond = cdf > u_t.double().unsqueeze(-1) * total
+    first = beyond.to(torch.int64).argmax(dim=-1)  # first candidate beyond the target
+    last_pos = (e.shape[-1] - 1) - (e > 0).flip(-1).to(torch.int64).argmax(dim=-1)
+    return torch.where(beyond.any(dim=-1), first, last_pos), cdf / total
+
+
 def smooth_ffbs(spec, xs, ws, start, u):
     """``_do_sample_ffbs`` (particle/base.py:105-134) with the ``Categorical(logits).sample()`` draws (not injectable in
-    the reference) realised by inverse CDF from the SAME logits: trajectory j takes the first candidate whose running
-    probability exceeds ``u[t, j]``.  ``start``: the resampled last state ``(N,[B],[D])``; ``u (S-1, N, [B])``."""
+    the reference) realised by inverse CDF from the SAME logits (``ffbs_backward_step``).  ``start``: the resampled last state
+    ``(N,[B],[D])``; ``u (S-1, N, [B])``."""
     res = [start]
     for t in range(len(xs) - 2, -1, -1):
-        logits = ffbs_logits(spec, xs[t], ws[t], res[-1])  # (N_j, N_i, [B])
-        if logits.dim() == 3:
-            logits = logits.moveaxis(1, 2)  # (N_j, B, N_i)
-        m = logits.max(dim=-1, keepdim=True)[0]
-        e = (logits - m).exp().double()
-        cdf = e.cumsum(dim=-1)
-        target = u[t].double().unsqueeze(-1) * cdf[..., -1:]
-        idx = (cdf > target).to(torch.int64).argmax(dim=-1)  # first candidate beyond the target
+        idx, _ = ffbs_backward_step(spec, xs[t], ws[t], res[-1], u[t])
         x_t = xs[t]
         if spec.dim > 0:
             res.append(x_t.gather(0, idx.unsqueeze(-1).expand(idx.shape + (spec.dim,))))
