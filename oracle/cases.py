@@ -125,11 +125,40 @@ CLUSTER_CASES = [
          ess_threshold=0.9, seed=203, dtypes=("f64", "f32"), no_smooth=True),
 ]
 
+# ---- half-observed rows: NaN in PART of an observation (``nan_cells``: (step, column of a (T, B) per-series y | component of an
+# O-vector y) pairs).  The reference calls an observation missing only when EVERY element is NaN (filters/base.py:212), so such a
+# row is a weighted move whose affected columns go NaN / -inf for that step and recover at the next fully observed one
+# (INTEGRATION.md).  Kept apart from CASES: the suites parametrised over those compare moments without ``equal_nan``; these are
+# compared by ``tests/helpers.py: assert_close_nan_aware`` (tests/test_oracle_golden.py, tests/test_partial_nan_gpu.py).  Every
+# case has a fully observed step after its last NaN cell.
+PARTIAL_NAN_CASES = [
+    # per-series y (T, B): column 1 half-observes steps 3 and 4 (back to back); step 9 is a WHOLE NaN row (a propagate-only move)
+    dict(name="sv_apf_boot_partnan", model="sv_batched", filter="apf", proposal="bootstrap", N=256, B=4, T=12,
+         ess_threshold=0.9, seed=301, nan_cells=((3, 1), (4, 1), (9, 0), (9, 1), (9, 2), (9, 3)), dtypes=("f64", "f32")),
+    dict(name="sv_sisr_boot_partnan", model="sv_batched", filter="sisr", proposal="bootstrap", N=256, B=4, T=12,
+         ess_threshold=0.6, seed=302, nan_cells=((2, 3), (5, 0), (6, 0)), dtypes=("f64",)),
+    # a shared O = 2 observation with one NaN component: every column is affected
+    dict(name="rw2d_sisr_boot_partnan", model="rw2d", filter="sisr", proposal="bootstrap", N=256, B=2, T=12,
+         ess_threshold=0.9, seed=303, nan_cells=((3, 0), (7, 1)), dtypes=("f64", "f32")),
+    # ... under the optimal proposal the PARTICLES go NaN, from that step to the end of the run
+    dict(name="rw2d_apf_lgo_partnan", model="rw2d", filter="apf", proposal="lgo", N=256, B=2, T=12,
+         ess_threshold=0.9, seed=304, nan_cells=((3, 0), (7, 1)), dtypes=("f64",)),
+    dict(name="rw2d_sisr_lgo_partnan", model="rw2d", filter="sisr", proposal="lgo", N=300, B=1, T=10,
+         ess_threshold=0.5, seed=305, nan_cells=((4, 1),), dtypes=("f64",)),
+    dict(name="lorenz_apf_boot_partnan", model="lorenz", filter="apf", proposal="bootstrap", N=128, B=2, T=10,
+         ess_threshold=0.9, seed=306, nan_cells=((3, 0), (6, 1)), dtypes=("f64", "f32")),
+    # column-cluster sizes (CLUSTER_CASES): B = 2 keeps the fixture under the largest committed one; step 4 is a whole NaN row
+    dict(name="sv_apf_boot_partnan_n4096", model="sv_batched", filter="apf", proposal="bootstrap", N=4096, B=2, T=6,
+         ess_threshold=0.9, seed=307, nan_cells=((2, 1), (4, 0), (4, 1)), dtypes=("f64", "f32"), no_smooth=True),
+    dict(name="rw2d_theta_sisr_boot_partnan_n2052", model="rw2d_theta_b", filter="sisr", proposal="bootstrap", N=2052, B=3, T=6,
+         ess_threshold=0.8, seed=308, nan_cells=((2, 0),), dtypes=("f64",), no_smooth=True),
+]
+
 _LORENZ_A_S = [0.8, 0.0, 0.3]
 _LORENZ_A_O3 = [[0.8, 0.1, 0.0], [-0.2, 0.9, 0.05], [0.0, 0.3, 0.7]]
 _RW2D_A_S = [1.0, 0.5]
 
-CASE_BY_NAME = {c["name"]: c for c in CASES + CLUSTER_CASES}
+CASE_BY_NAME = {c["name"]: c for c in CASES + CLUSTER_CASES + PARTIAL_NAN_CASES}
 # the cases whose model the fused kernels take (D > 1 or O == 1); ``lg1d_o2_*`` runs on the torch route (tests/test_torch_route_golden.py)
 FUSED_CASES = [c for c in CASES if c["model"] != "lg1d_o2"]
 
@@ -242,4 +271,6 @@ def simulate(case, spec: M.ModelSpec, dtype=torch.float64) -> torch.Tensor:
     y = torch.stack(ys)
     for s in case.get("nan_steps", ()):
         y[s] = float("nan")
+    for s, c in case.get("nan_cells", ()):  # one element of a row: column of a (T, B) y, component of a (T, O) y
+        y[s, c] = float("nan")
     return y

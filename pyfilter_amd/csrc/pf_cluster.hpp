@@ -60,7 +60,13 @@ namespace pf {
 #else
 #define PFK_MARK(n) do { } while (0)
 #endif
-#define PFK_FOLD (16 + 3 * 64)  // scalars | per chunk: inclusive prefix, exclusive prefix, factor
+// the fold of a state's records in LDS: 16 scalar slots | per chunk: inclusive prefix, exclusive prefix, factor.  Scalar slots:
+// 0 M1, 1 S1, 2 Q1, 3 M2, 4 S2, 5 flag bits, 6 .. 6 + 2 D - 1 the moments, PFK_FOLD_AUX the lse of the chunks' `aux_w`,
+// PFK_FOLD_U the column's systematic offset (wave 0's Philox draw)
+#define PFK_FOLD (16 + 3 * 64)
+#define PFK_FOLD_AUX 13
+#define PFK_FOLD_U 15
+static_assert(6 + 2 * PF_MAXD <= PFK_FOLD_AUX && PFK_FOLD_AUX < PFK_FOLD_U && PFK_FOLD_U < 16, "scalar slots of the fold");
 
 // pf_filter_observe: the theta update of an SMC^2 observation (pf_theta_step: w += ll, the running total, the (ESS, all finite) pair
 // on the device and in the polled host slot) folded into the run's tail - every column's bookkeeper writes its increment through and
@@ -225,7 +231,21 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
 
     // ---- publish: the records, scans and particles of the state in registers, as state `s` (local index) of this run -------------
     // rw of the NEXT move (cp.yn / cc.ybn hold its observation): lw + first-stage weights when that move is a weighted APF move
-    auto publish = [&](int s, bool two_next, bool poison_w) {
+    // log-sum-exp over a wave's chunk of VEC sanitised values per lane (-inf: no contribution; -inf when there is none)
+    auto wave_lse = [&](const T (&v)[VEC]) -> T {
+        T m = v[0];
+#pragma unroll
+        for (int j = 1; j < VEC; ++j) m = v[j] > m ? v[j] : m;
+        const T mw = wave_max<T>(m);
+        T sm = T(0);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) sm += (v[j] == -Lim<T>::inf()) ? T(0) : pf_exp_w(v[j] - mw);
+        sm = wave_sum<T>(sm);
+        return (T)((double)mw + log_sum<T>((double)sm));
+    };
+    // aux_w: see `flat` in the loop below - the chunk's lse of a SISR move's own weights, published in the slot of sum e^2 when
+    // the chunk's log-weights carry no information (an APF publishes the lse of its first-stage weights alone there)
+    auto publish = [&](int s, bool two_next, bool poison_w, T aux_w = -Lim<T>::inf()) {
         const int q = run.t0 + s;
         // the particles first: their stores travel while the sums and the scan below are computed (state 0 of a run is where
         // the caller left it)
@@ -263,8 +283,9 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
             if (FILT != PF_FILTER_APF || i != 1) v[i] = wave_sum<T>(v[i]);
         bool poison_pre = false;
         T er[VEC], mw2 = mw1;
+        const bool flat_chunk = !(mw1 > Lim<T>::lowest());  // (wave-uniform)
         if (two_next) {
-            T rw[VEC];
+            T rw[VEC], prs[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 T xj[D];
@@ -273,7 +294,9 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
                 const T pre = pre_weight<T, D>(md, proposal, cp, cc, xj, true);
                 if (on && is_nan_or_posinf(pre)) poison_pre = true;
                 rw[j] = on ? sanitize_logw(pre + lw[j]) : -Lim<T>::inf();
+                prs[j] = on ? sanitize_logw(pre) : -Lim<T>::inf();
             }
+            if (flat_chunk) aux_w = wave_lse(prs);
             T mm = rw[0];
 #pragma unroll
             for (int j = 1; j < VEC; ++j) mm = rw[j] > mm ? rw[j] : mm;
@@ -310,7 +333,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
             for (int i = 0; i < 3 * NG; ++i) w[i] = 0u;
             PfkWords<T>::put(w + 0 * NWT, mw1);
             PfkWords<T>::put(w + 1 * NWT, v[0]);
-            PfkWords<T>::put(w + 2 * NWT, v[1]);
+            PfkWords<T>::put(w + 2 * NWT, flat_chunk ? aux_w : v[1]);
             PfkWords<T>::put(w + 3 * NWT, (T)pbits);
 #pragma unroll
             for (int i = 0; i < 2 * D; ++i) PfkWords<T>::put(w + (4 + i) * NWT, v[2 + i]);
@@ -337,6 +360,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
     // is set by the traffic in the consumer CU's own memory queue); the other waves wait at the barrier and read the fold from LDS
     struct Fold {
         double M1, S1, Q1, M2, S2;
+        double aux;  // lse over the column of the chunks' `aux_w` (meaningful when the whole column is flat)
         double mom[2 * D];
         bool poison_w, poison_pre;
         const double *ci, *cex, *gg;  // per chunk, in LDS: inclusive / exclusive prefix of the rescaled chunk totals, the factors
@@ -390,7 +414,15 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
             const bool have = lane < nchunks;
             const T mw1 = have ? PfkWords<T>::get(w + 0 * NWT) : -Lim<T>::inf();
             const T s1 = have ? PfkWords<T>::get(w + 1 * NWT) : T(0);
-            const T q1 = have ? PfkWords<T>::get(w + 2 * NWT) : T(0);
+            // (a chunk without information in its log-weights - all -inf / lowest - carries `aux_w` in this slot: its own sum e^2 is
+            // its sum e, every e being 0 or 1)
+            const bool flatc = have && !(mw1 > Lim<T>::lowest());
+            const T q1raw = have ? PfkWords<T>::get(w + 2 * NWT) : T(0);
+            const T q1 = flatc ? s1 : q1raw;
+            const T ax = flatc ? q1raw : -Lim<T>::inf();
+            const T AXM = wave_max<T>(ax);
+            const T axs = wave_sum<T>((ax == -Lim<T>::inf()) ? T(0) : pf_exp_w(ax - AXM));
+            const double AUX = (double)AXM + log_sum<T>((double)axs);
             const unsigned pb = have ? (unsigned)PfkWords<T>::get(w + 3 * NWT) : (my_xcc << 4);
             const T mw2 = have ? PfkWords<T>::get(w + (4 + 2 * D) * NWT) : -Lim<T>::inf();
             const double tw = have ? PfkWords<double>::get(w + NT * NWT) : 0.0;
@@ -423,6 +455,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
                 fl[5] = (double)((pw ? 1 : 0) | (pp_ ? 2 : 0) | (one_xcd ? 4 : 0) | (dead ? 8 : 0));
 #pragma unroll
                 for (int i = 0; i < 2 * D; ++i) fl[6 + i] = mom[i];
+                fl[PFK_FOLD_AUX] = AUX;
             }
         }
         pfc_barrier(PFK_NW);
@@ -435,6 +468,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
         const int flags = (int)fl[5];
 #pragma unroll
         for (int i = 0; i < 2 * D; ++i) f.mom[i] = fl[6 + i];
+        f.aux = fl[PFK_FOLD_AUX];
         f.poison_w = (flags & 1) != 0;
         f.poison_pre = (flags & 2) != 0;
         if (s == 0) fastx = (flags & 4) != 0 && !cr.spread;
@@ -457,7 +491,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
                 a.means[((int64_t)row * g.B + b) * D + d] = (T)((double)piv[d] + dm);
                 a.vars[((int64_t)row * g.B + b) * D + d] = (T)var;
             }
-            piv[d] = (T)((double)piv[d] + dm);
+            if (dm == dm) piv[d] = (T)((double)piv[d] + dm);  // (a state without weight - NaN row - leaves the pivot where it was)
         }
     };
 
@@ -481,12 +515,42 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
 
     bool obs_nx = obs_flag(0);
     load_yn(0, obs_nx);
+    // A piece behind a per-step piece whose last move - a SISR move on top of a column whose log-weights carried no information
+    // (ColStat::flat_pending; `flat` in the loop below) - left its increment pending: lse(wi) - log N over that move's own weights, under
+    // Bootstrap log p(y[t0 - 1] | x) of the particles in registers.  Every chunk publishes its share with state 0 (`aux_w`).
+    T aux0 = -Lim<T>::inf();
+    bool pend_flat = false;
+    if (run.t0 > 0 && !apf && proposal == PF_PROP_BOOTSTRAP) {
+        const ColStat st = a.stat[b];  // (every thread; member 0 rewrites the record when the run is over)
+        pend_flat = !st.ll_done && st.prev_observed && st.flat_pending;
+        if (pend_flat) {
+            const T* yr = y_row(run.t0 - 1);
+            // (a copy, opaque to the optimiser: k_fused_column has the account)
+            ColParams<T, D> cpp = cp;
+#pragma unroll
+            for (int o = 0; o < ColParams<T, D>::MAXO; ++o) {
+                cpp.y[o] = yr[o < O ? o : 0];
+                asm volatile("" : "+v"(cpp.ob[o]), "+v"(cpp.os[o]));
+#pragma unroll
+                for (int d = 0; d < D; ++d) asm volatile("" : "+v"(cpp.A[o][d]));
+            }
+            T wv[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                T xj[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) xj[d] = x[d][j];
+                wv[j] = on ? sanitize_logw(obs_logpdf<T, D>(md, cpp, xj)) : -Lim<T>::inf();
+            }
+            aux0 = wave_lse(wv);
+        }
+    }
     cc.set_obs(cp);
-    publish(0, apf && obs_nx, false);
+    publish(0, apf && obs_nx, false, aux0);
 
     T ll_tot = T(0);
     double base_prev = 0.0;
-    bool obs_prev = false, prepoison_prev = false;
+    bool obs_prev = false, prepoison_prev = false, flatw_prev = false;
     const bool book = (k == 0 && tid == 0);
     if (book) ll_tot = a.ll_total[b];
 
@@ -525,19 +589,23 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
         // other waves read it with the fold) - every thread drawing the same number cost ~100 VALU per wave and step
         T u = T(0);
         if (a.u_tape) u = a.u_tape[(int64_t)t * g.B + b];
-        else if (wid == 0) fold_lds[(s & 1) * PFK_FOLD + 15] = (double)uniform_draw<T>(seed, PF_STREAM_UNIFORM, (uint32_t)t, (uint64_t)b);
+        else if (wid == 0) fold_lds[(s & 1) * PFK_FOLD + PFK_FOLD_U] = (double)uniform_draw<T>(seed, PF_STREAM_UNIFORM, (uint32_t)t, (uint64_t)b);
 
         PFK_MARK(20_draws_done);
         // ---- the state's records: moments row t, log-likelihood increment of the previous move, the decision -------------------
         const Fold f = poll_fold(s);
-        if (!a.u_tape) u = (T)fold_lds[(s & 1) * PFK_FOLD + 15];
+        if (!a.u_tape) u = (T)fold_lds[(s & 1) * PFK_FOLD + PFK_FOLD_U];
         write_moments(t, f);
         const double lse_w = f.M1 + log_sum<T>(f.S1);
+        // A column whose log-weights are all -inf / the lowest finite value (what a half-observed row leaves behind, and where a
+        // SISR column then stays: k_fused_column has the account).  W is uniform; the log-likelihood terms come from the move's own
+        // weights - `Fold::aux`, the lse of what the chunks published in place of their sum e^2.  Uniform per column.
+        const bool flat = !(f.M1 > (double)Lim<T>::lowest());
         if (book) {
             if (s > 0) {
                 double ll = 0.0;
                 if (obs_prev) {
-                    ll = lse_w - base_prev;
+                    ll = flatw_prev ? f.aux - a.logN : lse_w - base_prev;
                     if (f.poison_w || prepoison_prev) ll = __builtin_nan("");
                 }
                 a.ll_steps[(int64_t)(t - 1) * g.B + b] = (T)ll;
@@ -550,7 +618,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
                     const int pslot = (run.t0 - 1) & 3;
                     double ll = 0.0;
                     if (st.prev_observed) {
-                        ll = lse_w - st.base_lse;
+                        ll = pend_flat ? f.aux - a.logN : lse_w - st.base_lse;
                         if (a.poison[pslot * g.B + b]) ll = __builtin_nan("");
                     }
                     a.ll_steps[(int64_t)(run.t0 - 1) * g.B + b] = (T)ll;
@@ -560,14 +628,33 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
         }
         PFK_MARK(30_fold_books_done);
         const bool resample = apf ? obs : (f.S1 * f.S1 / f.Q1 < a.thr_abs);  // apf.py:29-31 | sisr.py:18-19
+        const bool flat_w = flat && obs && !apf && !resample;  // a SISR move that weighs on top of such a column
         double base_lse = lse_w;
         bool poison = false;
         int idx[VEC];
         T xr[VEC][D];
-        if (resample) {
+        if (resample && !(f.S2 > 0.0)) {
+            // every resampling weight NaN / +inf (a half-observed row under an APF): the reference's normalised weights are NaN and
+            // searchsorted over their cumsum - NaN below its pinned last entry, 1 - hands out N - 1 everywhere (resampling.py:44-50)
+            base_lse = a.logN;  // (the move's ll is NaN: poison_pre)
+            T xl[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                T tail[VEC];
+                pfk_load_vec<T, VEC>(x_plane(t, d), N - VEC, tail);
+                xl[d] = tail[VEC - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                idx[j] = N - 1;
+#pragma unroll
+                for (int d = 0; d < D; ++d) xr[j][d] = xl[d];
+            }
+        } else if (resample) {
             const double inv_tot = inv_sum<T>(f.S2);
             if (two) base_lse = a.logN - ((f.M2 + log_sum<T>(f.S2)) - lse_w);  // apf.py:44
             else base_lse = a.logN;
+            if (two && flat) base_lse = a.logN - (f.aux - a.logN);  // apf.py:44 with W = 1 / N: log mean exp(pre)
             T pp[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) pp[j] = pow2 ? (T(i0 + j) + u) * rcN : grid_position<T>(i0 + j, u, nT);
@@ -679,6 +766,10 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
 
         PFK_MARK(70_ancestors_done);
         // ---- propagate, weigh (the per-particle model code of the other routes) -----------------------------------------------------
+        if (flat_w) {  // (the move's own weights alone; the weighing below stays the expression it is for every other column)
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) lw[j] = T(0);
+        }
         T lw_new[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
@@ -690,7 +781,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
                     if (on && is_nan_or_posinf(w_new)) poison = true;
                 } else {
                     if (on && is_nan_or_posinf(wi)) poison = true;
-                    w_new = resample ? wi : (wi + lw[j]);  // sisr.py:52-55
+                    w_new = resample ? wi : (wi + lw[j]);  // sisr.py:52-55 (flat_w: lw is 0 here, the sum is formed below)
                 }
             } else {  // NaN observation: propagate only, weights carried, ll = 0 (particle/state.py:38-42)
                 sample_and_weight<T, D>(md, PF_PROP_BOOTSTRAP, cp, cc, xr[j], z[j], xn);
@@ -707,11 +798,21 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
 #pragma unroll
             for (int d = 0; d < D; ++d) x[d][j] = xr[j][d];
         }
+        T aux_w = -Lim<T>::inf();
+        if (flat_w) {
+            // sisr.py:52-56 on such a column: ll = lse(wi) - log N, and the new log-weight wi + lowest IS the lowest finite value
+            // again - unless wi is NaN / +inf, which stays -inf
+            aux_w = wave_lse(lw_new);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j)
+                if (on) lw[j] = (lw_new[j] == -Lim<T>::inf()) ? -Lim<T>::inf() : Lim<T>::lowest();
+        }
         PFK_MARK(80_model_done);
         base_prev = base_lse;
         obs_prev = obs;
+        flatw_prev = flat_w;
         prepoison_prev = f.poison_pre;
-        publish(s + 1, apf && obs_nx, poison);
+        publish(s + 1, apf && obs_nx, poison, aux_w);
         PFK_MARK(90_published);
     }
 
@@ -728,7 +829,7 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
         if (book) {
             double ll = 0.0;
             if (obs_prev) {
-                ll = lse_w - base_prev;
+                ll = flatw_prev ? f.aux - a.logN : lse_w - base_prev;
                 if (f.poison_w || prepoison_prev) ll = __builtin_nan("");
             }
             if (cr.th.enabled) st1_sc1<T>(a.ll_steps, (int)((int64_t)(q_out - 1) * g.B + b), (T)ll);  // (read by another column's workgroup)

@@ -291,8 +291,34 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
                 a.means[((int64_t)row * g.B + b) * D + d] = (T)((double)piv[d] + dm);
                 a.vars[((int64_t)row * g.B + b) * D + d] = (T)var;
             }
-            piv[d] = (T)((double)piv[d] + dm);
+            if (dm == dm) piv[d] = (T)((double)piv[d] + dm);  // (a state without weight - NaN row - leaves the pivot where it was)
         }
+    };
+    // log-sum-exp over the column of VEC sanitised values per lane (-inf: no contribution).  Off the common path: the
+    // log-likelihood terms of a column whose weights carry no information (below).  Two barriers; uses recA.
+    auto column_lse = [&](const T (&v)[VEC]) -> double {
+        T m = v[0];
+#pragma unroll
+        for (int j = 1; j < VEC; ++j) m = v[j] > m ? v[j] : m;
+        const T mw = wave_max<T>(m);
+        T s = T(0);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) s += (v[j] == -Lim<T>::inf()) ? T(0) : pf_exp_w(v[j] - mw);
+        s = wave_sum<T>(s);
+        double M = (double)mw, S = (double)s;
+        if (nw > 1) {
+            if (lane == 0) {
+                recA[2 * wid] = (double)mw;
+                recA[2 * wid + 1] = (double)s;
+            }
+            pfc_barrier(nw);
+            M = recA[0];
+            for (int w = 1; w < nw; ++w) M = recA[2 * w] > M ? recA[2 * w] : M;
+            S = 0.0;
+            for (int w = 0; w < nw; ++w) S += recA[2 * w + 1] * exp_diff_t<T>(recA[2 * w], M);
+            pfc_barrier(nw);
+        }
+        return M + log_sum<T>(S);
     };
 
     {
@@ -302,6 +328,37 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
     }
     T ll_tot = (tid == 0) ? a.ll_total[b] : T(0);
     double lse_w = M1 + log_sum<T>(S1);
+    // ... and when that pending move was a SISR move on top of a column whose log-weights carried no information (ColStat::flat_pending;
+    // `flat` in the loop below), its increment is lse(wi) - log N over the move's own weights: under Bootstrap those are
+    // log p(y[t0 - 1] | x) of the particles in registers (column_bookkeeping does the same on its route)
+    double ll_pend = 0.0;
+    bool pend_flat = false;
+    if (run.t0 > 0) {
+        const ColStat st = a.stat[b];  // (every thread: uniform)
+        pend_flat = !st.ll_done && st.prev_observed && st.flat_pending && !apf && !user && proposal == PF_PROP_BOOTSTRAP;
+        if (pend_flat) {
+            const T* yr = y_row(run.t0 - 1);
+            // (a copy, opaque to the optimiser: shared with this branch, a subexpression of the run's own constants - log s times
+            // ln 2 - is no longer contracted into the fused multiply-add it is everywhere else, and the constant moves by an ulp)
+            ColParams<T, D> cpp = cp;
+#pragma unroll
+            for (int o = 0; o < ColParams<T, D>::MAXO; ++o) {
+                cpp.y[o] = yr[o < O ? o : 0];
+                asm volatile("" : "+v"(cpp.ob[o]), "+v"(cpp.os[o]));
+#pragma unroll
+                for (int d = 0; d < D; ++d) asm volatile("" : "+v"(cpp.A[o][d]));
+            }
+            T wv[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                T xj[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) xj[d] = x[d][j];
+                wv[j] = ok[j] ? sanitize_logw(obs_logpdf<T, D>(md, cpp, xj)) : -Lim<T>::inf();
+            }
+            ll_pend = column_lse(wv) - a.logN;
+        }
+    }
     if (run.t0 > 0 && tid == 0) {
         // A run issued in pieces: the piece before this one may have been a per-step piece WITHOUT finalize, whose last
         // move's log-likelihood increment is still pending - the per-step route flushes it one launch later, from the
@@ -313,7 +370,7 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
             const int pslot = (run.t0 - 1) & 3;
             double ll = 0.0;
             if (st.prev_observed) {
-                ll = lse_w - st.base_lse;
+                ll = pend_flat ? ll_pend : lse_w - st.base_lse;
                 if (a.poison[pslot * g.B + b]) ll = __builtin_nan("");
             }
             a.ll_steps[(int64_t)(run.t0 - 1) * g.B + b] = (T)ll;
@@ -357,12 +414,19 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
         const T u_tape = u_nx;
         request_inputs(s + 1);
         bool poison = false;
+        // A column whose log-weights are all -inf / the lowest finite value - the state a half-observed row leaves behind (every
+        // weight NaN -> -inf) and what a SISR column stays in from then on: the reference's nan_to_num_ maps -inf to the lowest
+        // finite value and adding anything to that changes nothing.  Its W is uniform, and its log-likelihood terms are formed
+        // from the step's own weights (lse(w') - lse(w) has nothing to telescope over): `flat` paths below.  Uniform per column.
+        const bool flat = !(M1 > (double)Lim<T>::lowest());
 
         // ---- resampling weights, the decision -----------------------------------------------------------------------------------
         T rw[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) rw[j] = lw[j];
+        double lse_pre = 0.0;  // flat && two: lse of the first-stage weights alone
         if (two) {
+            T prs[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 T xj[D];
@@ -378,9 +442,12 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
                 const T pre = pre_weight<T, D>(md, proposal, cp, cc, xj, false, um);
                 if (ok[j] && is_nan_or_posinf(pre)) poison = true;
                 rw[j] = ok[j] ? sanitize_logw(pre + lw[j]) : -Lim<T>::inf();
+                prs[j] = ok[j] ? sanitize_logw(pre) : -Lim<T>::inf();
             }
+            if (flat) lse_pre = column_lse(prs);
         }
         const bool resample = apf ? obs : (S1 * S1 / Q1 < a.thr_abs);  // apf.py:29-31 | sisr.py:18-19
+        const bool flat_w = flat && obs && !apf && !resample;  // a SISR move that weighs on top of such a column
         double base_lse = lse_w;
         int idx[VEC];
         T xr[VEC][D];
@@ -429,6 +496,7 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
             const double inv_tot = inv_sum<T>(S);
             if (two) base_lse = a.logN - ((Mr + log_sum<T>(S)) - lse_w);  // apf.py:44
             else base_lse = a.logN;                                        // W = 1 / N after resampling
+            if (two && flat) base_lse = a.logN - (lse_pre - a.logN);       // apf.py:44 with W = 1 / N: log mean exp(pre)
             if (on) {
                 T cv[VEC];
 #pragma unroll
@@ -489,9 +557,12 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
             // (the rounds unrolled with the positions as BYTE offsets - 16 VALU per round of four positions against 21 for a run-time
             // loop over element indices: sorted_lower_bound, pf_device.hpp)
             sorted_lower_bound<T, VEC, 4096>(cdfs, np2, pp, q);
+            // every resampling weight NaN / +inf (a half-observed row under an APF): the reference's normalised weights are NaN and
+            // searchsorted over their cumsum - NaN below its pinned last entry, 1 - hands out N - 1 everywhere (resampling.py:44-50)
+            const bool no_weight = !(S > 0.0);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                idx[j] = q[j] > N - 1 ? N - 1 : q[j];
+                idx[j] = (no_weight || q[j] > N - 1) ? N - 1 : q[j];
 #pragma unroll
                 for (int d = 0; d < D; ++d) xr[j][d] = xs[d * NP + idx[j]];
             }
@@ -530,6 +601,25 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
                 if (!ragged) draw_normals<T, D, VEC>(seed, PF_STREAM_NORMAL, (uint32_t)t, (uint64_t)((int64_t)b * N + i0), z);
                 else draw_normals_ragged<T, D, VEC>(seed, PF_STREAM_NORMAL, (uint32_t)t, (uint64_t)((int64_t)b * N + i0), z);
             }
+        }
+        double ll_flat = 0.0;
+        if (flat_w) {
+            // sisr.py:52-56 on such a column: ll = lse(wi) - log N (W uniform) over the move's own weights - evaluated here, ahead
+            // of the weighing loop, which stays what it is for every other column: wi + lw is -inf there and is stored as the lowest
+            // finite value, as the reference's wi + lowest is - unless wi is NaN / +inf, which stays -inf
+            T wv[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                T xq[D];
+                UserMS<T, D> um = UserMS<T, D>::none();
+                if constexpr (user) {
+                    um.gather(a.user_loc, a.user_scale, (int64_t)b * N, (int64_t)g.B * N, idx[j], a.user_scale_percol != 0, b, g.B);
+                    um.euler(xr[j], a.user_dt);
+                }
+                const T wq = sample_and_weight<T, D>(md, proposal, cp, cc, xr[j], z[j], xq, um);
+                wv[j] = ok[j] ? sanitize_logw(wq) : -Lim<T>::inf();
+            }
+            ll_flat = column_lse(wv) - a.logN;
         }
         T lw_new[VEC];
 #pragma unroll
@@ -579,7 +669,7 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
         if (tid == 0) {
             double ll = 0.0;
             if (obs) {
-                ll = lse_w - base_lse;
+                ll = flat_w ? ll_flat : lse_w - base_lse;
                 if (any_poison) ll = __builtin_nan("");
             }
             a.ll_steps[(int64_t)t * g.B + b] = (T)ll;

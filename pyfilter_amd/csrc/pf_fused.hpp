@@ -135,7 +135,13 @@ template <typename T> struct FusedArgs {
     }
     // pivot of the weighted-moment partials of state q (see t0), component d of column b
     template <int D> __device__ __forceinline__ T pivot(int q, int b, int d) const {
-        return (q - 2 >= t0) ? means[((int64_t)(q - 2) * g.B + b) * D + d] : (T)piv0[(int64_t)b * PF_MAXD + d];
+        // (a state without weight - every log-weight -inf after a half-observed row - has a NaN row: the run's record stands in;
+        // step_body forms the same value)
+        if (q - 2 >= t0) {
+            const T m = means[((int64_t)(q - 2) * g.B + b) * D + d];
+            if (m == m) return m;
+        }
+        return (T)piv0[(int64_t)b * PF_MAXD + d];
     }
     int debug_cut;  // development knob (env PF_DEBUG_CUT): kernels return early after stage n; 0 = off
     int keep_state;  // per launch: the state this step writes is read by somebody other than the next launch - a recorded state
@@ -860,7 +866,9 @@ __device__ __forceinline__ void spacing_table(const double* part, int64_t stride
 // The column's bookkeeping, run by one extra workgroup per column: moments of the current state (row `step` of
 // filter_means / filter_variance), the log-likelihood increment of the previous step, the bases of this one.
 // Reads the partials of state `step` only - nothing the step workgroups of the same launch write or wait for.
-template <typename T, int D>
+// FLATFIX: the log-likelihood terms of a column whose log-weights carry no information are formed here, from the column's
+// particles (below) - every caller but the one-column leaf, whose column (one scalar series) cannot be half-observed.
+template <typename T, int D, bool FLATFIX = true>
 __device__ __forceinline__ void column_bookkeeping(const FusedArgs<T>& a, int b, double* red, double* redm) {
     const Geom& g = a.g;
     const int step = a.step;
@@ -895,6 +903,58 @@ __device__ __forceinline__ void column_bookkeeping(const FusedArgs<T>& a, int b,
     const double ess = c1.S * c1.S / c1.Q;
     bool resample = apf ? obs : (ess < a.thr_abs);  // apf.py:29-31 | sisr.py:18-19 (the step workgroups: the same test)
     if (a.finalize_only) resample = false;
+    // A column whose log-weights are all -inf / the lowest finite value - what a half-observed row leaves behind (every weight
+    // NaN -> -inf), and where a SISR column stays from then on: the reference's nan_to_num_ maps -inf to the lowest finite value,
+    // and adding anything to that changes nothing.  Its W is uniform and its log-likelihood terms come from the move's own
+    // weights: lse(w') - lse(w) has nothing to telescope over (the difference came out +inf, or 0).  They are re-evaluated here,
+    // over the column's stored particles, by the whole workgroup - rare, and off every other column's path:
+    //   APF, this move (apf.py:44 with W = 1 / N): log mean exp(pre-weight of the incoming particles under y[step]);
+    //   SISR + Bootstrap, the PREVIOUS move (sisr.py:52-56): its weights were log p(y[step - 1] | x), x the particles it wrote -
+    //   this launch's incoming state.  (Under LinearGaussianObservations a half-observed row leaves NaN particles: no such
+    //   move has a finite increment.)  Anything else - a user-defined process - reports NaN for such a move.
+    const bool flat = !(c1.M > (double)Lim<T>::lowest());
+    bool fix_base = false, fix_ll = false;
+    double fix = 0.0;
+    if constexpr (FLATFIX) {
+        const ColStat su = a.stat[b];  // (every thread: the branch below is uniform)
+        const bool builtin = a.md.hid_kind != PF_HID_USER_AFFINE;
+        fix_base = two && flat && builtin;
+        fix_ll = !apf && step > 0 && !su.ll_done && su.prev_observed && su.flat_pending && builtin && a.proposal == PF_PROP_BOOTSTRAP;
+        __syncthreads();  // every wave has read the record before thread 0, past this barrier, rewrites it: one decision for all
+        if (fix_base || fix_ll) {
+            ColParams<T, D> cp;
+            ColConsts<T, D> cc;
+            load_col_params<T, D>(a, b, fix_ll ? step - 1 : step, true, cp);
+            cc.prepare(a.md, cp);
+            cc.set_obs(cp);
+            const T* const xin = a.x[step & 1];
+            OnlineLse<T> acc;
+            acc.init();
+            for (int64_t i = threadIdx.x; i < g.N; i += PF_BLOCK) {
+                T xj[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) xj[d] = xin[((int64_t)d * g.B + b) * g.N + i];
+                const T v = fix_ll ? obs_logpdf<T, D>(a.md, cp, xj) : pre_weight<T, D>(a.md, a.proposal, cp, cc, xj, false);
+                double rs, e;
+                acc.push(sanitize_logw(v), rs, e);
+            }
+            const T mw = wave_max<T>(acc.m);
+            const double sw = wave_sum(acc.s * ((acc.m == -Lim<T>::inf()) ? 0.0 : (double)pf_exp_w(acc.m - mw)));
+            __syncthreads();  // (red / redm: the column sums above are done with them)
+            if ((threadIdx.x & 63) == 0) {
+                redm[threadIdx.x >> 6] = (double)mw;
+                red[threadIdx.x >> 6] = sw;
+            }
+            __syncthreads();
+            double M = redm[0];
+#pragma unroll
+            for (int w = 1; w < PF_NWAVES; ++w) M = redm[w] > M ? redm[w] : M;
+            double S = 0.0;
+#pragma unroll
+            for (int w = 0; w < PF_NWAVES; ++w) S += red[w] * exp_diff_t<T>(redm[w], M);
+            fix = M + log(S);
+        }
+    }
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {  // moments of the current state -> row `step` of filter_means / filter_variance
@@ -908,7 +968,7 @@ __device__ __forceinline__ void column_bookkeeping(const FusedArgs<T>& a, int b,
         if (step > 0 && !st.ll_done) {
             double ll = 0.0;
             if (st.prev_observed) {
-                ll = lse_w - st.base_lse;
+                ll = fix_ll ? fix - a.logN : lse_w - st.base_lse;
                 if (poisoned) ll = __builtin_nan("");
             }
             a.poison[pslot * g.B + b] = 0;
@@ -920,9 +980,13 @@ __device__ __forceinline__ void column_bookkeeping(const FusedArgs<T>& a, int b,
         st.ll_done = a.finalize_only ? 1 : 0;
         if (!a.finalize_only) {
             st.prev_observed = obs ? 1 : 0;
+            st.flat_pending = (!apf && obs && flat && !resample) ? 1 : 0;  // a SISR move that weighs on top of a flat column
             // ll_t = [lse(w') - log N] + [lse(rw) - lse(w)] (apf.py:44) | lse(wi + log W), W = 1/N after resampling
             // else the carried weights (sisr.py:52-55)
             st.base_lse = apf ? a.logN - ((c2.M + log(c2.S)) - lse_w) : (resample ? a.logN : lse_w);
+            // (see `flat` above; a SISR column of -inf AND lowest weights whose ESS falls below the threshold resamples: W = 1 / N
+            // after it, log N as in every resampling move - k_fused_column / k_fused_cluster say the same)
+            if (obs && flat) st.base_lse = fix_base ? a.logN - (fix - a.logN) : ((!apf && resample) ? a.logN : __builtin_nan(""));
         }
         a.stat[b] = st;
     }
@@ -1681,8 +1745,10 @@ __device__ __forceinline__ void step_body(const FusedArgs<T>& a, const StepShare
                 piv[0] = hx.piv;
             } else {
 #pragma unroll
-                for (int d = 0; d < D; ++d)
+                for (int d = 0; d < D; ++d) {
                     piv[d] = (step - 1 >= a.t0) ? la->means[((int64_t)(step - 1) * g.B + b) * D + d] : (T)la->piv0[(int64_t)b * PF_MAXD + d];
+                    if (piv[d] != piv[d]) piv[d] = (T)la->piv0[(int64_t)b * PF_MAXD + d];  // (a NaN row: FusedArgs::pivot)
+                }
             }
             // the next resampling weights (scanned chunk by chunk below); the partial accumulator keeps the weights' own
             // family (moments, ll, ESS)
@@ -1893,7 +1959,7 @@ __global__ __launch_bounds__(PF_BLOCK, (ONECOL ? PF_WAVES_LEAF : StepWaves<T, D,
     // filter_run_impl.  (The round-2 layout (tiles + 1, B) interleaved the bookkeepers with the columns: 2 - 3 us per step slower.)
     if (!a.book_inline && PF_STEP_K == (unsigned)a.g.tiles) {
         PF_BOOK_STAMP(a, PF_STEP_B, 6);
-        column_bookkeeping<T, D>(a, PF_STEP_B, red, redb);
+        column_bookkeeping<T, D, !ONECOL>(a, PF_STEP_B, red, redb);
         PF_BOOK_STAMP(a, PF_STEP_B, 7);
         return;
     }
@@ -1911,7 +1977,7 @@ __global__ __launch_bounds__(PF_BLOCK, (ONECOL ? PF_WAVES_LEAF : StepWaves<T, D,
         else step_body<T, D, VEC, MODE, PROP, FAST, SPEC, MK, false, MULTI>(a, sh, pl, z0);
     }
     if (a.book_inline == 1 && PF_STEP_K == (unsigned)a.g.tiles - 1u)  // (reads the partials of the incoming state only)
-        column_bookkeeping<T, D>(a, PF_STEP_B, red, redb);
+        column_bookkeeping<T, D, !ONECOL>(a, PF_STEP_B, red, redb);
 }
 
 // clears the per-column records of a fresh run (see filter_run_impl)

@@ -70,7 +70,8 @@ struct ColStat {
     int resample;      // this step resamples this column
     int prev_observed; // the previous step was a weighted (observed) step
     int ll_done;       // the previous step's log-likelihood was already flushed by a finalize-only pass
-    int pad;
+    int flat_pending;  // (per-step route) the previous step was a SISR move that weighed on top of a column whose log-weights were
+                       // all -inf / lowest: its increment is re-evaluated from the particles (column_bookkeeping)
 };
 
 // workspace carve-up (all offsets 256-byte aligned)

@@ -14,6 +14,23 @@ def load_golden(name, dt):
         return {k: torch.from_numpy(f[k]) for k in f.files}
 
 
+def assert_close_nan_aware(got, want, rtol, atol, what=""):
+    """``got`` against ``want`` where ``want`` may hold NaN / +-inf ON PURPOSE (half-observed rows, ``oracle/cases.py:
+    PARTIAL_NAN_CASES``): the NaN pattern must be the same ELEMENTWISE, the +-inf pattern too (sign included), and everything
+    else is within ``rtol`` / ``atol``.  (``assert_close(equal_nan=True)`` alone would do, this says which of the three failed.)"""
+    got, want = torch.as_tensor(got).detach().cpu(), torch.as_tensor(want).detach().cpu()
+    assert got.shape == want.shape, f"{what}: shape {tuple(got.shape)} against {tuple(want.shape)}"
+    gn, wn = got.isnan(), want.isnan()
+    assert torch.equal(gn, wn), (f"{what}: NaN pattern differs at {int((gn != wn).sum())} of {wn.numel()} elements "
+                                 f"(got {int(gn.sum())} NaN, want {int(wn.sum())}); first at {(gn != wn).nonzero()[0].tolist()}: "
+                                 f"got {got[gn != wn][0].item()}, want {want[gn != wn][0].item()}")
+    gi, wi = got.isinf(), want.isinf()
+    assert torch.equal(gi, wi) and torch.equal(got[gi], want[wi]), \
+        f"{what}: +-inf pattern differs (got {int(gi.sum())} inf, want {int(wi.sum())})"
+    rest = ~(wn | wi)
+    torch.testing.assert_close(got[rest], want[rest], rtol=rtol, atol=atol, msg=lambda m: f"{what}: {m}")
+
+
 def moves_after(g, t):
     """Moves a filter has made once it has consumed ``t`` observations of fixture ``g`` (= the time index of that state):
     ``t`` unless the model is observed every k-th step only (``move_of_obs``, oracle/make_golden.py)."""

@@ -8,9 +8,11 @@ import pytest
 import torch
 
 from oracle import cpu_ref
-from oracle.cases import CASE_BY_NAME, CASES, CLUSTER_CASES, build_spec
+from oracle.cases import CASE_BY_NAME, CASES, CLUSTER_CASES, PARTIAL_NAN_CASES, build_spec
+from tests.helpers import assert_close_nan_aware
 
 DT = {"f64": torch.float64, "f32": torch.float32}
+PARTIAL_PARAMS = [(c["name"], d) for c in PARTIAL_NAN_CASES for d in c["dtypes"]]
 PARAMS = [(c["name"], d) for c in CASES for d in c["dtypes"]]
 # (+ the reference's runs at column-cluster sizes, round 6: filtering arrays only)
 FILTER_PARAMS = PARAMS + [(c["name"], d) for c in CLUSTER_CASES for d in c["dtypes"]]
@@ -41,6 +43,86 @@ def test_filter_matches_reference(golden_dir, name, dt):
     torch.testing.assert_close(out["filter_means"], g["filter_means"], **tol)
     torch.testing.assert_close(out["filter_variance"], g["filter_variance"], **tol)
     torch.testing.assert_close(out["loglikelihood"], g["loglikelihood"], **tol)
+
+
+def _tol(dt):
+    return dict(rtol=1e-12, atol=1e-13) if dt == "f64" else dict(rtol=2e-5, atol=2e-6)
+
+
+@pytest.mark.parametrize("name,dt", PARTIAL_PARAMS)
+def test_half_observed_rows_match_reference(golden_dir, name, dt):
+    """Rows that are NaN in only SOME elements (``oracle/cases.py: PARTIAL_NAN_CASES``): the reference weighs them
+    (``y.isnan().all()``, filters/base.py:212) and the affected columns go NaN / -inf for the step.  The oracle against the
+    unmodified reference's arrays: identical ancestors, identical NaN and +-inf patterns, the rest at this file's tolerances."""
+    case = CASE_BY_NAME[name]
+    dtype = DT[dt]
+    g = load(golden_dir, name, dt)
+    spec = build_spec(case, dtype)
+    out = cpu_ref.batch_filter(
+        spec, case["filter"], case["proposal"], g["y"], g["x0"], g["z_tape"].to(dtype), g["u_tape"].to(dtype),
+        ess_threshold=case["ess_threshold"], record_steps=True,
+    )
+    assert torch.equal(out["step_idx"], g["step_idx"]), "ancestor indices differ from the reference"
+    for k in ("step_x", "step_w", "step_ll", "filter_means", "filter_variance", "loglikelihood"):
+        assert_close_nan_aware(out[k], g[k], what=f"{name}/{dt} {k}", **_tol(dt))
+
+
+def half_observed_steps(case, g):
+    """``(T, B)`` bool: column b weighs a partly-NaN observation at step t (some NaN, not all) - per column for a per-series
+    ``(T, B)`` y, every column for a shared ``(T, O)`` row - and ``(T,)`` bool: the whole row is NaN (a propagate-only move)."""
+    y = g["y"]
+    t_len, b = y.shape[0], case["B"]
+    nan = y.isnan().reshape(t_len, -1)
+    whole = nan.all(1)
+    if case["model"] == "sv_batched":  # one scalar series per column
+        return nan & ~whole.unsqueeze(1), whole
+    return (nan.any(1) & ~whole).unsqueeze(1).expand(t_len, b), whole
+
+
+@pytest.mark.parametrize("name,dt", PARTIAL_PARAMS)
+def test_half_observed_fixtures_hold_the_semantics_they_pin(golden_dir, name, dt):
+    """What the reference does to a half-observed column, read off the fixtures themselves - so that a regenerated fixture
+    cannot silently lose its half-observed steps.  At such a step t of column b: ``step_ll`` NaN, recorded weights all -inf,
+    moments row t + 1 NaN, an APF's ancestors all N - 1 (searchsorted over a NaN cdf whose last entry is 1), the run's
+    log-likelihood NaN.  Columns that never see one stay finite throughout.  Under Bootstrap the column RECOVERS at its next
+    fully observed step (finite ll and moments; a SISR column then sits at the lowest finite log-weight); under
+    LinearGaussianObservations the proposal's mean takes the NaN, the particles are NaN from that step to the end of the run
+    and nothing recovers - the fixture is asserted to show exactly that."""
+    case = CASE_BY_NAME[name]
+    g = load(golden_dir, name, dt)
+    n, b, t_len = case["N"], case["B"], case["T"]
+    half, whole = half_observed_steps(case, g)
+    assert half.any(), "no half-observed step in the fixture"
+    ll, w, idx = g["step_ll"].reshape(t_len, b), g["step_w"], g["step_idx"]
+    means = g["filter_means"].reshape(t_len + 1, b, -1)
+    lgo = case["proposal"] == "lgo"
+    lowest = torch.finfo(DT[dt]).min
+    recovered = 0
+    for col in range(b):
+        dead = prev_hit = False  # (dead - lgo: the column's particles are NaN from its first half-observed step on)
+        for t in range(t_len):
+            if whole[t]:
+                continue
+            x_nan = g["step_x"][t][:, col].isnan()
+            if bool(half[t, col]) or dead:
+                assert ll[t, col].isnan() and means[t + 1, col].isnan().all(), (t, col)
+                assert (w[t][:, col] == -math.inf).all(), (t, col)
+                if case["filter"] == "apf":
+                    assert (idx[t][:, col] == n - 1).all(), (t, col)
+                assert x_nan.all() if lgo else not x_nan.any(), (t, col)
+                dead, prev_hit = lgo, True
+            else:
+                assert ll[t, col].isfinite() and means[t + 1, col].isfinite().all() and not x_nan.any(), (t, col)
+                if prev_hit:  # the next fully observed step: the column is back
+                    recovered += 1
+                    if case["filter"] == "sisr":
+                        assert (w[t][:, col] == lowest).all(), (t, col)
+                prev_hit = False
+        touched = bool(half[:, col].any())
+        assert g["loglikelihood"].reshape(b)[col].isnan() == touched, col
+        if not touched:
+            assert ll[:, col].isfinite().all() and means[:, col].isfinite().all() and w[:, :, col].isfinite().all(), col
+    assert lgo or recovered >= 1, "no column recovers at a fully observed step"
 
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])
