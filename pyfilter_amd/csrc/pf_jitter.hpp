@@ -228,7 +228,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_jitter_apply(ThetaPriors pr, const
             double u = loc + std * e;
             if (discrete) u = (1.0 - s) * xj + s * u;
             double x, lp;
-            theta_prior(pr.kind[p], pr.a[p], pr.b[p], u, x, lp);
+            theta_prior<T>(pr.kind[p], pr.a[p], pr.b[p], u, x, lp);
             u_out[(int64_t)i * P + p] = (T)u;
             reinterpret_cast<T*>(out.x[p])[i] = (T)x;
         }

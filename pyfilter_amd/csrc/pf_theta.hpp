@@ -26,8 +26,24 @@ struct ThetaOut {  // the P parameter tensors (B,) theta* is written to
 __device__ __forceinline__ double th_softplus(double v) { return v > 0.0 ? v + log1p(exp(-v)) : log1p(exp(v)); }
 __device__ __forceinline__ double th_xlogy(double x, double y) { return x == 0.0 ? 0.0 : x * log(y); }
 
+// the sigmoid of the unit-interval bijection, clamped as torch's SigmoidTransform clamps it: to [finfo(T).tiny, 1 - finfo(T).eps] of
+// the TENSORS' type - float64's bounds round to 0 and 1 in float32, the closed ends of an open support
+template <typename T> struct ThetaClamp;
+template <> struct ThetaClamp<double> {
+    static constexpr double lo = 2.2250738585072014e-308, hi = 1.0 - 2.220446049250313e-16;
+};
+template <> struct ThetaClamp<float> {
+    static constexpr double lo = 1.1754943508222875e-38, hi = 1.0 - 1.1920928955078125e-07;
+};
+template <typename T>
+__device__ __forceinline__ double th_sigmoid(double u) {
+    const double s = 1.0 / (1.0 + exp(-u));
+    return s < ThetaClamp<T>::lo ? ThetaClamp<T>::lo : (s > ThetaClamp<T>::hi ? ThetaClamp<T>::hi : s);
+}
+
 // constrained value x = bijection(u) of prior `kind` and log p(x) + log |dx / du|: the density of u (prior.py:98-123 -
-// `TransformedDistribution(prior, biject_to(support).inv).log_prob(u)` with torch's own formulas per family)
+// `TransformedDistribution(prior, biject_to(support).inv).log_prob(u)` with torch's own formulas per family); T: the tensors' type
+template <typename T>
 __device__ __forceinline__ void theta_prior(int kind, double a, double b, double u, double& x, double& lp) {
     const double half_log_2pi = 0.91893853320467274178;
     switch (kind) {
@@ -60,16 +76,12 @@ __device__ __forceinline__ void theta_prior(int kind, double a, double b, double
             break;
         }
         case PF_PRIOR_BETA: {  // concentration1 a, concentration0 b; unit interval: x = sigmoid(u) (clamped as torch clamps it)
-            double s = 1.0 / (1.0 + exp(-u));
-            s = s < 2.2250738585072014e-308 ? 2.2250738585072014e-308 : (s > 1.0 - 2.220446049250313e-16 ? 1.0 - 2.220446049250313e-16 : s);
-            x = s;
+            x = th_sigmoid<T>(u);
             lp = th_xlogy(a - 1.0, x) + th_xlogy(b - 1.0, 1.0 - x) + lgamma(a + b) - lgamma(a) - lgamma(b) - th_softplus(-u) - th_softplus(u);
             break;
         }
         default: {  // PF_PRIOR_UNIFORM: low a, high b; x = a + (b - a) sigmoid(u)
-            double s = 1.0 / (1.0 + exp(-u));
-            s = s < 2.2250738585072014e-308 ? 2.2250738585072014e-308 : (s > 1.0 - 2.220446049250313e-16 ? 1.0 - 2.220446049250313e-16 : s);
-            x = a + (b - a) * s;
+            x = a + (b - a) * th_sigmoid<T>(u);
             lp = -log(b - a) - th_softplus(-u) - th_softplus(u) + log(fabs(b - a));
             break;
         }
@@ -164,7 +176,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_theta_fit(const T* __restrict__ va
             for (int p = 0; p < P; ++p)
                 for (int q = 0; q < P; ++q) {
                     const double d = sc[p * PF_THETA_MAXP + p];
-                    sl[p * PF_THETA_MAXP + q] = (p == q) ? sqrt(d > 0.0 ? d : 0.0) : 0.0;
+                    // (a negative diagonal counts as 0; a NaN one - a NaN among the values - stays NaN, as torch's clamp leaves it)
+                    sl[p * PF_THETA_MAXP + q] = (p == q) ? sqrt(d < 0.0 ? 0.0 : d) : 0.0;
                 }
         }
         for (int p = 0; p < P; ++p) {
@@ -193,7 +206,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_theta_propose(ThetaPriors pr, cons
             for (int q = 0; q <= p; ++q) u += (double)chol[p * P + q] * e[q];
             u = (double)(T)u;  // (the value the caller keeps - and every later evaluation starts from - is the stored one)
             double x, l1;
-            theta_prior(pr.kind[p], pr.a[p], pr.b[p], u, x, l1);
+            theta_prior<T>(pr.kind[p], pr.a[p], pr.b[p], u, x, l1);
             lp += l1;
             u_out[i * P + p] = (T)u;
             reinterpret_cast<T*>(out.x[p])[i] = (T)x;

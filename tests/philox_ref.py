@@ -17,7 +17,7 @@ Everything is evaluated in float64 whatever ``dtype`` says: ``dtype`` selects th
 kernels' float32 transcendentals are somebody else's business (the tests compare within bars that a wrong word overshoots by
 orders of magnitude).
 
-The jitter and theta kernels' draws are not restated here."""
+The jitter kernel's draws are restated on top of this module by ``tests/theta_oracle.py::jitter_draws``."""
 import numpy as np
 
 M32 = np.uint64(0xFFFFFFFF)

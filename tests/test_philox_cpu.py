@@ -3,7 +3,7 @@ known answers, the address maps of every draw the kernels make are injective, th
 should, and the INPUT CONDITION of the ancestor checks of ``tests/test_philox_draws_gpu.py`` holds - few resampling positions
 within ``delta`` of a cdf entry, for every shape and teacher state those tests use.
 
-The jitter and theta kernels' draws are not covered (``tests/philox_ref.py``)."""
+The jitter kernel's draws: ``tests/theta_oracle.py`` and ``tests/test_theta_oracle_cpu.py``."""
 import os
 import re
 

@@ -78,8 +78,18 @@ def test_theta_propose_is_the_priors_bijections_and_densities(dtype):
     total = 0.0
     for i, (name, prior) in enumerate(ref.priors.items()):
         ui = u[:, i].double()
-        torch.testing.assert_close(theta[name].double(), prior.get_constrained(ui), **_tol(dtype))
-        total = total + prior.unconstrained.log_prob(ui)
+        if dtype == torch.float32 and name in ("f", "g"):
+            # float32 tensors: the sigmoid is clamped at float32's tiny and 1 - eps (torch's SigmoidTransform per dtype) - row 1 drives
+            # the Beta parameter to u = 20.9, where that clamp binds; float64 torch does not state it, the host oracle does
+            from tests import theta_oracle
+
+            x, lpi = theta_oracle.prior(int(packed.kind[i]), float(packed.a[i]), float(packed.b[i]), ui.cpu().numpy(), "float32")
+            want_x, lpi = torch.from_numpy(x).cuda(), torch.from_numpy(lpi).cuda()
+            assert float(theta[name].max()) < (1.0 if name == "f" else 1.3)
+        else:
+            want_x, lpi = prior.get_constrained(ui), prior.unconstrained.log_prob(ui)
+        torch.testing.assert_close(theta[name].double(), want_x, **_tol(dtype))
+        total = total + lpi
     ok = torch.isfinite(total)
     assert ok.sum() >= b - 2
     tol = _tol(dtype) if dtype == torch.float64 else dict(rtol=2e-6, atol=2e-5)
@@ -381,7 +391,11 @@ def test_theta_resample_is_normalize_then_systematic(dtype, b):
             want = theta_systematic(theta_normalize(lw.double()), u)
             if dtype == torch.float64:
                 assert torch.equal(got, want), (case, u, int((got != want).sum()))
-            else:  # float32 cdf and grid: a position within rounding of a cdf step may land on the neighbour
+            else:  # float32 cdf and grid: only a position within delta_32 of the float64 cdf entry between them may take the neighbour
+                from tests import philox_ref, theta_cases, theta_oracle
+
+                _, cdf, pos = theta_oracle.systematic(lw.double().numpy(), u, "float32")
+                assert philox_ref.valid_ancestor(got.numpy(), pos, cdf, theta_cases.DELTA32).all()
                 assert int((got - want).abs().max()) <= 1 and int((got != want).sum()) <= max(2, b // 200)
             if case == 2 and u > 0:  # (u = 0: position 0 sits AT cdf[0] = 0 and takes ancestor 0, as searchsorted has it)
                 assert bool((got == b // 3).all())
