@@ -160,7 +160,8 @@ int pf_columns_exchange(void* dst, const void* src, const uint8_t* mask, int64_t
                         int elem_bytes, void* stream);
 
 /* pyfilter.filters.particle.utils.log_likelihood (particle/utils.py:7-22): max v + log sum W exp(v - max);
- * W == NULL means 1/N.  v (B,N) is NOT sanitised (a NaN poisons the column, as in the reference). out (B). */
+ * W == NULL means 1/N.  v (B,N) is NOT sanitised (a NaN poisons the column, and a column that is -inf throughout gives NaN, as
+ * in the reference). out (B). */
 int pf_loglik(const void* v, const void* W, void* out, int64_t N, int64_t B, int dtype, void* ws, size_t ws_bytes,
               void* stream);
 

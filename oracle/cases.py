@@ -154,11 +154,23 @@ PARTIAL_NAN_CASES = [
          ess_threshold=0.8, seed=308, nan_cells=((2, 0),), dtypes=("f64",), no_smooth=True),
 ]
 
+# ---- a state far from zero: the OU model of ``ou_batched`` with ``gamma`` at a price level (1e4) and an initial law that starts
+# there, so that level / spread is >= 1e5 at EVERY recorded step (asserted from the fixtures, tests/test_moments_oracle_cpu.py).
+# A variance taken from raw second moments loses (level / spread)^2 * 2^-53 of itself there; ``sum W (x - mean)^2`` - the
+# reference - does not.  Kept apart from CASES: tests/test_moments_parity_gpu.py compares every route on them.  No smoothing arrays.
+LEVEL = 1.0e4
+LEVEL_CASES = [
+    dict(name="ou_level_sisr_boot", model="ou_level", filter="sisr", proposal="bootstrap", N=256, B=3, T=12,
+         ess_threshold=0.8, seed=401, dtypes=("f64", "f32"), no_smooth=True),
+    dict(name="ou_level_apf_lgo", model="ou_level", filter="apf", proposal="lgo", N=128, B=3, T=12,
+         ess_threshold=0.9, seed=402, dtypes=("f64", "f32"), no_smooth=True),
+]
+
 _LORENZ_A_S = [0.8, 0.0, 0.3]
 _LORENZ_A_O3 = [[0.8, 0.1, 0.0], [-0.2, 0.9, 0.05], [0.0, 0.3, 0.7]]
 _RW2D_A_S = [1.0, 0.5]
 
-CASE_BY_NAME = {c["name"]: c for c in CASES + CLUSTER_CASES + PARTIAL_NAN_CASES}
+CASE_BY_NAME = {c["name"]: c for c in CASES + CLUSTER_CASES + PARTIAL_NAN_CASES + LEVEL_CASES}
 # the cases whose model the fused kernels take (D > 1 or O == 1); ``lg1d_o2_*`` runs on the torch route (tests/test_torch_route_golden.py)
 FUSED_CASES = [c for c in CASES if c["model"] != "lg1d_o2"]
 
@@ -246,6 +258,12 @@ def _build_spec(case, dtype=torch.float64) -> M.ModelSpec:
         gamma = t([0.0 + 0.1 * i for i in range(b)])
         sigma = t([0.05 + 0.01 * i for i in range(b)])
         return M.ModelSpec(M.HID_OU, (kappa, gamma, sigma), 0, 1.0, (0.0, 0.1), M.OBS_LINEAR, (1.0, 0.0, 0.05), 0)
+    if m == "ou_level":  # ou_batched at a level: gamma = level + 0.1 i, x0 ~ N(level, 0.05); case["level"]: 1e4 (the fixtures)
+        level = float(case.get("level", LEVEL))
+        kappa = t([0.025 * (i + 1) for i in range(b)])
+        gamma = t([level + 0.1 * i for i in range(b)])
+        sigma = t([0.05 + 0.01 * i for i in range(b)])
+        return M.ModelSpec(M.HID_OU, (kappa, gamma, sigma), 0, 1.0, (level, 0.05), M.OBS_LINEAR, (1.0, 0.0, 0.05), 0)
     raise KeyError(m)
 
 
@@ -256,7 +274,7 @@ def simulate(case, spec: M.ModelSpec, dtype=torch.float64) -> torch.Tensor:
     t_len = case["T"]
     b = case["B"]
     per_series = case["model"] == "sv_batched"
-    shape = (1, b) if (per_series or (case["model"] in ("ou_batched", "rw2d_theta", "rw2d_theta_b") or bool(case.get("per_filter")))) else (1, 1)
+    shape = (1, b) if (per_series or (case["model"] in ("ou_batched", "ou_level", "rw2d_theta", "rw2d_theta_b") or bool(case.get("per_filter")))) else (1, 1)
     if spec.dim > 0:
         shape = shape + (spec.dim,)
     x = M.initial_sample(spec, torch.randn(shape, generator=g, dtype=dtype))

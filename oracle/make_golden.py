@@ -62,7 +62,7 @@ def _main_child(dtype_name: str, only=None):
     import torch.distributions.multivariate_normal as mvn_mod
 
     from oracle import models as M
-    from oracle.cases import CASES, CLUSTER_CASES, PARTIAL_NAN_CASES, build_spec, simulate
+    from oracle.cases import CASES, CLUSTER_CASES, LEVEL_CASES, PARTIAL_NAN_CASES, build_spec, simulate
 
     # ---------------------------------------------------------------------------------------------------------
     class Tape:
@@ -163,7 +163,7 @@ def _main_child(dtype_name: str, only=None):
     # ---------------------------------------------------------------------------------------------------------
     os.makedirs(GOLDEN, exist_ok=True)
 
-    for case in CASES + CLUSTER_CASES + PARTIAL_NAN_CASES:
+    for case in CASES + CLUSTER_CASES + PARTIAL_NAN_CASES + LEVEL_CASES:
         if dtype_name not in case["dtypes"] or (only is not None and case["name"] not in only):
             continue
         oes = int(case.get("observe_every_step", 1))

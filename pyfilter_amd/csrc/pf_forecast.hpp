@@ -8,10 +8,14 @@
 // Per step and particle:   x <- loc(x) + scale(x) * inc * z          (mean_scale / the ColConsts closed forms: Bootstrap's move)
 //                          m_o(x), s_o(x): the observation's conditional mean and scale
 //                              linear: b + A x, s        stochastic volatility: b, x
-// and in double            sum W, sum W x_d, sum W x_d^2, sum W m_o, sum W (m_o^2 + s_o^2)
+// and in double            sum W, sum W (x_d - c_d), sum W (x_d - c_d)^2, sum W (m_o - k_o), sum W ((m_o - k_o)^2 + s_o^2)
+// about pivots every tile and launch geometry agrees on (ForecastPivot): c = the INPUT cloud's first particle of the column walked
+// the same H moves WITHOUT noise (so it drifts with the cloud: an AR(1) at a level loses 1 % of it per step), k = its image under
+// the observation's conditional mean (s_o^2 is a genuine second moment and is not pivoted).  The pivot is a function of the
+// parameters and of that one particle alone.  A cloud far from zero keeps its variance to rounding; the subtraction is in double.
 // The observation's moments are Rao-Blackwellised (the law of total variance): no observation noise is drawn for them.
-// Conventions of k_moments_final: the weights are taken as normalised (no division by sum W), the variance
-// S2 - 2 mu S1 + mu^2 S0 is clamped at 0, a NaN poisons its row.
+// Conventions of k_moments_final: the weights are taken as normalised (no division by sum W): mean = c S0 + P1, the variance
+// P2 - 2 (mean - c) P1 + (mean - c)^2 S0 is clamped at 0, a NaN poisons its row.
 //
 // No per-thread array is indexed by the run-time step or by a run-time dimension (such arrays live in scratch memory): the
 // accumulators are per STEP - reduced across the workgroup and stored at the end of each step - not per horizon.  The tiles'
@@ -67,6 +71,33 @@ __device__ __forceinline__ void forecast_normals(const T* __restrict__ tape, int
     else draw_normals_ragged<T, K, PF_FC_ITEMS>(seed, stream, (uint32_t)h, (uint64_t)col0, v);
 }
 
+// the pivot of column b's sums: start() reads the input cloud's first particle, step() moves it as forecast_move moves a particle
+// whose draw is 0 and takes the observation's conditional mean of it
+template <typename T, int D> struct ForecastPivot {
+    static constexpr int MAXO = ObsDim<D>::MAXO;
+    T xp[D];
+    double cx[D], cm[MAXO];
+    __device__ __forceinline__ void start(const T* __restrict__ x, int b, int B, int64_t N) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) xp[d] = x[((int64_t)d * B + b) * N];
+    }
+    __device__ __forceinline__ void step(const ModelDesc& md, const ColParams<T, D>& cp, const ColConsts<T, D>& cc, bool sv) {
+        T zero[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) zero[d] = T(0);
+        forecast_move<T, D>(md, cp, cc, xp, zero);
+#pragma unroll
+        for (int d = 0; d < D; ++d) cx[d] = (double)xp[d];
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o) {
+            T lo = cp.ob[o];
+#pragma unroll
+            for (int d = 0; d < D; ++d) lo += cp.A[o][d] * xp[d];
+            cm[o] = (double)(sv ? cp.ob[o] : lo);
+        }
+    }
+};
+
 template <typename T, int D>
 __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const T* __restrict__ params, int H, const T* __restrict__ x,
                                                             const T* __restrict__ W, const T* __restrict__ z, const T* __restrict__ e,
@@ -87,6 +118,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
     const int64_t col0 = (int64_t)b * N + i0;
     const int64_t left = N - i0;  // particles of this thread: min(left, IT), none when <= 0
     const bool whole = (N % IT) == 0;
+    ForecastPivot<T, D> pv;
+    pv.start(x, b, B, N);
 
     T xv[IT][D];
     double w[IT];
@@ -102,6 +135,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
         T zv[IT][D], ev[IT][MAXO];
         forecast_normals<T, D>(z, D, seed, PF_STREAM_FORECAST_Z, h, plane, col0, left, whole, zv);
         if (y_path) forecast_normals<T, MAXO>(e, O, seed, PF_STREAM_FORECAST_E, h, plane, col0, left, whole, ev);
+        pv.step(md, cp, cc, sv);
         double acc[Q];
 #pragma unroll
         for (int q = 0; q < Q; ++q) acc[q] = 0.0;
@@ -121,7 +155,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
                 acc[0] += w[k];
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    const double xd = (double)xv[k][d];
+                    const double xd = (double)xv[k][d] - pv.cx[d];
                     acc[1 + d] += w[k] * xd;
                     acc[1 + D + d] += w[k] * xd * xd;
                     if (x_path) x_path[((int64_t)h * D + d) * plane + col0 + k] = xv[k][d];
@@ -129,7 +163,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
 #pragma unroll
                 for (int o = 0; o < MAXO; ++o) {
                     if (o < O) {
-                        const double mo = (double)m[o], so = (double)s[o];
+                        const double mo = (double)m[o] - pv.cm[o], so = (double)s[o];
                         acc[1 + 2 * D + o] += w[k] * mo;
                         acc[1 + 2 * D + MAXO + o] += w[k] * (mo * mo + so * so);
                         if (y_path) y_path[((int64_t)h * O + o) * plane + col0 + k] = m[o] + s[o] * ev[k][o];
@@ -159,11 +193,14 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
 }
 
 // grid (H, B): the tiles' sums of one step and filter -> x_mean, x_var (H, B, D) and y_mean, y_var (H, B, O)
-template <typename T>
-__global__ __launch_bounds__(PF_BLOCK) void k_forecast_final(const double* __restrict__ part, T* __restrict__ x_mean, T* __restrict__ x_var,
-                                                             T* __restrict__ y_mean, T* __restrict__ y_var, int D, int O, int B, int tiles) {
+// (params, x: k_forecast_part's, for the pivots of its sums - thread 0 walks the pivot to its step)
+template <typename T, int D>
+__global__ __launch_bounds__(PF_BLOCK) void k_forecast_final(ModelDesc md, const T* __restrict__ params, const T* __restrict__ x,
+                                                             const double* __restrict__ part, T* __restrict__ x_mean, T* __restrict__ x_var,
+                                                             T* __restrict__ y_mean, T* __restrict__ y_var, int64_t N, int B, int tiles) {
     __shared__ double red[PF_FC_Q * PF_NWAVES];
     const int h = blockIdx.x, b = blockIdx.y;
+    const int O = md.obs_dim;
     const int64_t stride = (int64_t)B * tiles;
     const double* row = part + (int64_t)h * PF_FC_Q * stride + (int64_t)b * tiles;
     double acc[PF_FC_Q];
@@ -178,22 +215,31 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_final(const double* __res
     block_sum<PF_FC_Q>(acc, red);
     if (threadIdx.x == 0) {
         const int64_t hb = (int64_t)h * B + b;
+        ColParams<T, D> cp;
+        cp.load(params + (int64_t)b * (4 * D + O * D + 2 * O), O, nullptr);
+        ColConsts<T, D> cc;
+        cc.prepare(md, cp);
+        // (a pivot that differed from k_forecast_part's in its last bit would move the mean by that bit and the variance not at
+        // all: c enters mean - c only through c (S0 - 1))
+        ForecastPivot<T, D> pv;
+        pv.start(x, b, B, N);
+        for (int s = 0; s <= h; ++s) pv.step(md, cp, cc, md.obs_kind == PF_OBS_SV);
+        const double (&cx)[D] = pv.cx;
+        const double (&cm)[ObsDim<D>::MAXO] = pv.cm;
 #pragma unroll
-        for (int d = 0; d < PF_MAXD; ++d) {
-            if (d < D) {
-                const double mu = acc[FC_X + d];  // sum W x  (no division by sum W: k_moments_final)
-                const double v = acc[FC_XX + d] - 2.0 * mu * acc[FC_X + d] + mu * mu * acc[FC_W];
-                x_mean[hb * D + d] = (T)mu;
-                x_var[hb * D + d] = (T)(v < 0.0 ? 0.0 : v);
-            }
+        for (int d = 0; d < D; ++d) {
+            const double r = cx[d] * (acc[FC_W] - 1.0) + acc[FC_X + d];  // mean - c  (mean = sum W x: k_moments_final)
+            x_mean[hb * D + d] = (T)(cx[d] + r);
+            x_var[hb * D + d] = (T)pivoted_variance(acc[FC_W], acc[FC_X + d], acc[FC_XX + d], r);
         }
 #pragma unroll
-        for (int o = 0; o < PF_MAXO; ++o) {
+        for (int o = 0; o < ObsDim<D>::MAXO; ++o) {
             if (o < O) {
-                const double mu = acc[FC_M + o];
-                const double v = acc[FC_MM + o] - 2.0 * mu * acc[FC_M + o] + mu * mu * acc[FC_W];
+                const double r = cm[o] * (acc[FC_W] - 1.0) + acc[FC_M + o];
+                const double mu = cm[o] + r;
+                const double v = pivoted_variance(acc[FC_W], acc[FC_M + o], acc[FC_MM + o], r);
                 y_mean[hb * O + o] = (T)mu;
-                y_var[hb * O + o] = (T)(v < 0.0 ? 0.0 : v);
+                y_var[hb * O + o] = (T)v;
             }
         }
     }

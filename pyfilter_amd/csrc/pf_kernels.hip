@@ -973,10 +973,20 @@ __global__ __launch_bounds__(PF_BLOCK) void k_loglik_final(const double* __restr
     __shared__ double redm[PF_NWAVES];
     const int b = blockIdx.x;
     const ColLse c = combine_partials<T>(part, PQ_M1, PQ_S1, -1, b, 0, g.B, g.tiles, red, redm);
-    if (threadIdx.x == 0) out[b] = (T)(c.M + log(c.S));
+    // (a column that is -inf throughout: NaN, the reference's -inf + log sum exp(-inf - -inf) - not the -inf of M + log 0)
+    if (threadIdx.x == 0) out[b] = (T)(c.M == -__builtin_huge_val() ? __builtin_nan("") : c.M + log(c.S));
 }
 
-// moments partials from normalised weights: sum W, sum W x_d, sum W x_d^2
+// the variance about the mean from sums about a pivot c: S0 = sum W, P1 = sum W (x - c), P2 = sum W (x - c)^2, r = mean - c.
+// Not contracted into fmas: one particle of weight 1 gives P2 = r P1 = r^2 S0 rounded alike, and a variance of exactly 0.
+__device__ __forceinline__ double pivoted_variance(double s0, double p1, double p2, double r) {
+#pragma clang fp contract(off)
+    const double v = p2 - 2.0 * r * p1 + r * r * s0;
+    return v < 0.0 ? 0.0 : v;  // (a NaN stays)
+}
+
+// moments partials from normalised weights about the pivot c_d = the column's first particle (every tile of a column reads the
+// same one; the subtraction in double, after widening): sum W, sum W (x_d - c_d), sum W (x_d - c_d)^2
 template <typename T>
 __global__ __launch_bounds__(PF_BLOCK) void k_moments_part(const T* __restrict__ x, const T* __restrict__ W,
                                                            double* __restrict__ part, Geom g, int D) {
@@ -987,13 +997,16 @@ __global__ __launch_bounds__(PF_BLOCK) void k_moments_part(const T* __restrict__
     double acc[1 + 2 * PF_MAXD];
 #pragma unroll
     for (int q = 0; q < 1 + 2 * PF_MAXD; ++q) acc[q] = 0.0;
+    double c[PF_MAXD];
+#pragma unroll
+    for (int d = 0; d < PF_MAXD; ++d) c[d] = d < D ? (double)x[((int64_t)d * g.B + b) * g.N] : 0.0;
     for (int64_t i = base + threadIdx.x; i < end; i += PF_BLOCK) {
         const double w = (double)W[(int64_t)b * g.N + i];
         acc[0] += w;
 #pragma unroll
         for (int d = 0; d < PF_MAXD; ++d) {
             if (d < D) {
-                const double xv = (double)x[((int64_t)d * g.B + b) * g.N + i];
+                const double xv = (double)x[((int64_t)d * g.B + b) * g.N + i] - c[d];
                 acc[1 + d] += w * xv;
                 acc[1 + PF_MAXD + d] += w * xv * xv;
             }
@@ -1010,9 +1023,14 @@ __global__ __launch_bounds__(PF_BLOCK) void k_moments_part(const T* __restrict__
 
 // (D here: the planes of this launch, <= PF_MAXD; pf_moments launches once per group of PF_MAXD planes and the row of a column
 // in mean / var is `ld` long, the group's first plane at `d0`)
+// With S0 = sum W and P1, P2 the sums about the pivot c (k_moments_part; x: the group's planes, for c):
+//   mean = c S0 + P1 = sum W x (the reference does not divide by sum W),
+//   var = P2 - 2 (mean - c) P1 + (mean - c)^2 S0 = sum W (x - mean)^2, clamped at 0 - it does not cancel however far the cloud
+//   sits from zero.  A NaN in a component (under any weight, 0 included) makes that component's mean and variance NaN.
 template <typename T>
-__global__ __launch_bounds__(PF_BLOCK) void k_moments_final(const double* __restrict__ part, T* __restrict__ mean,
-                                                            T* __restrict__ var, Geom g, int D, int d0, int ld) {
+__global__ __launch_bounds__(PF_BLOCK) void k_moments_final(const double* __restrict__ part, const T* __restrict__ x,
+                                                            T* __restrict__ mean, T* __restrict__ var, Geom g, int D, int d0,
+                                                            int ld) {
     __shared__ double red[(1 + 2 * PF_MAXD) * PF_NWAVES];
     const int b = blockIdx.x;
     const int64_t stride = (int64_t)g.B * g.tiles;
@@ -1025,10 +1043,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_moments_final(const double* __rest
     block_sum<1 + 2 * PF_MAXD>(acc, red);
     if (threadIdx.x == 0) {
         for (int d = 0; d < D; ++d) {
-            const double mu = acc[1 + d];  // sum W x  (the reference does not divide by sum W)
-            const double v = acc[1 + PF_MAXD + d] - 2.0 * mu * acc[1 + d] + mu * mu * acc[0];
+            const double c = (double)x[((int64_t)d * g.B + b) * g.N];
+            const double r = c * (acc[0] - 1.0) + acc[1 + d];  // mean - c
+            const double mu = c + r;
             mean[(int64_t)b * ld + d0 + d] = (T)mu;
-            var[(int64_t)b * ld + d0 + d] = (T)(v < 0.0 ? 0.0 : v);
+            var[(int64_t)b * ld + d0 + d] = (T)pivoted_variance(acc[0], acc[1 + d], acc[1 + PF_MAXD + d], r);
         }
     }
 }
@@ -1521,7 +1540,7 @@ extern "C" int pf_moments(const void* x, const void* W, void* mean, void* var, i
         for (int64_t d0 = 0; d0 < D; d0 += PF_MAXD) {
             const int dg = (int)((D - d0) < PF_MAXD ? (D - d0) : PF_MAXD);
             hipLaunchKernelGGL((k_moments_part<T>), p.grid, dim3(PF_BLOCK), 0, p.st, (const T*)x + d0 * plane, (const T*)W, p.part, p.g, dg);
-            hipLaunchKernelGGL((k_moments_final<T>), dim3(p.g.B), dim3(PF_BLOCK), 0, p.st, (const double*)p.part, (T*)mean, (T*)var, p.g,
+            hipLaunchKernelGGL((k_moments_final<T>), dim3(p.g.B), dim3(PF_BLOCK), 0, p.st, (const double*)p.part, (const T*)x + d0 * plane, (T*)mean, (T*)var, p.g,
                                dg, (int)d0, (int)D);
             PF_CHECK_LAUNCH();
         }
@@ -1636,8 +1655,8 @@ extern "C" int pf_forecast(const pf_model* model, int steps, const void* x, cons
         return with_d3(model->dim, [&](auto d) {
             hipLaunchKernelGGL((k_forecast_part<T, decltype(d)::value>), dim3(tiles, (int)B), dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
                                steps, (const T*)x, (const T*)W, (const T*)z, (const T*)e, seed, (double*)ws, (T*)x_path, (T*)y_path, N, (int)B);
-            hipLaunchKernelGGL((k_forecast_final<T>), dim3(steps, (int)B), dim3(PF_BLOCK), 0, st, (const double*)ws, (T*)x_mean, (T*)x_var,
-                               (T*)y_mean, (T*)y_var, (int)model->dim, (int)model->obs_dim, (int)B, tiles);
+            hipLaunchKernelGGL((k_forecast_final<T, decltype(d)::value>), dim3(steps, (int)B), dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
+                               (const T*)x, (const double*)ws, (T*)x_mean, (T*)x_var, (T*)y_mean, (T*)y_var, N, (int)B, tiles);
             return launch_status();
         });
     });

@@ -10,8 +10,8 @@ or tapes), not torch's global generator.
 * anything else (user callables, ``LinearModel``, a scalar state under a vector observation, CPU tensors): ``torch_forecast``, the
   same outputs from the same tapes as torch operations.
 
-Moments follow ``get_filter_mean_and_variance``: weights are taken as normalised, the variance ``S2 - 2 mu S1 + mu^2 S0`` is
-clamped at 0."""
+Moments follow ``get_filter_mean_and_variance``: weights are taken as normalised (no division by ``sum W``) and the variance is
+``sum W (x - mean)^2`` - centred before squaring (the kernel: sums about a pivot), so a cloud far from zero keeps it."""
 from typing import Optional
 
 import torch
@@ -36,14 +36,14 @@ class Forecast:
 
 def mix_forecasts(w: torch.Tensor, fc: Forecast) -> Forecast:
     """The mixture of ``B`` filters' forecasts (moments ``(steps, B, ...)``) under the normalised weights ``w (B,)`` - the
-    posterior predictive of SMC2 / NESS: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + mean_b^2) - mean^2`` (clamped at
-    0).  Evaluated in float64, returned in the forecasts' type."""
+    posterior predictive of SMC2 / NESS: ``mean = sum_b w_b mean_b``, ``var = sum_b w_b (var_b + (mean_b - mean)^2)`` (the members'
+    means centred before squaring: no cancellation at a level far from zero).  Evaluated in float64, returned in the forecasts' type."""
     def mix(mean, var):
         m, v = mean.double(), var.double()
         ww = w.to(device=m.device, dtype=torch.float64).reshape((1, -1) + (1,) * (m.dim() - 2))
         mu = (ww * m).sum(1)
-        second = (ww * (v + m * m)).sum(1)
-        return mu.to(mean.dtype), (second - mu * mu).clamp_min(0.0).to(var.dtype)
+        mixed = (ww * (v + (m - mu.unsqueeze(1)) ** 2)).sum(1)
+        return mu.to(mean.dtype), mixed.clamp_min(0.0).to(var.dtype)
 
     xm, xv = mix(fc.x_mean, fc.x_variance)
     ym, yv = mix(fc.y_mean, fc.y_variance)
@@ -108,11 +108,12 @@ def kernel_forecast(ctx, obs_event: bool, x: TimeseriesState, w: Optional[torch.
     return Forecast(shaped(xm, ctx.has_event), shaped(xv, ctx.has_event), shaped(ym, obs_event), shaped(yv, obs_event), path)
 
 
-def _weighted(w: torch.Tensor, first: torch.Tensor, second: torch.Tensor, dtype):
-    """``(sum W first, sum W second - 2 mu sum W first + mu^2 sum W)`` over dim 0 in float64, the variance clamped at 0."""
+def _weighted(w: torch.Tensor, first: torch.Tensor, within, dtype):
+    """``(mu = sum W first, sum W ((first - mu)^2 + within))`` over dim 0 in float64 (``first`` float64; ``within``: a variance
+    around ``first``, or 0.0) - centred before squaring, as ``get_filter_mean_and_variance``."""
     ww = w.double().reshape(w.shape + (1,) * (first.dim() - w.dim()))
     mu = (ww * first).sum(0)
-    var = (ww * second).sum(0) - 2.0 * mu * mu + mu * mu * ww.sum(0)
+    var = (ww * ((first - mu) ** 2 + within)).sum(0)
     return mu.to(dtype), var.clamp_min(0.0).to(dtype)
 
 
@@ -156,8 +157,8 @@ def torch_forecast(model, x: TimeseriesState, w: Optional[torch.Tensor], steps: 
         dens = model.build_density(x)
         m, var = dens.mean, dens.variance
         m, var = torch.broadcast_tensors(m, var)
-        xm, xv = _weighted(w, value.double(), value.double() ** 2, dtype)
-        ym, yv = _weighted(w, m.double(), m.double() ** 2 + var.double(), dtype)
+        xm, xv = _weighted(w, value.double(), 0.0, dtype)
+        ym, yv = _weighted(w, m.double(), var.double(), dtype)
         for k, v in zip(("xm", "xv", "ym", "yv"), (xm, xv, ym, yv)):
             rows[k].append(v)
         if paths:

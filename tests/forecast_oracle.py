@@ -12,7 +12,7 @@ weighted sums in float64; the moments are returned in the inputs' dtype."""
 import torch
 
 from oracle import models as M
-from oracle.cases import CASES, build_spec
+from oracle.cases import CASES, LEVEL_CASES, build_spec
 from tests.nested_cases import rounded_spec
 
 GPU_MODELS = ("lg1d", "sine", "sv_batched", "ou_batched", "rw2d_theta", "lorenz_o1", "lorenz_o3")  # D = 1, 2, 3; O = 1, 2, 3; per-filter rows
@@ -23,8 +23,16 @@ WEIGHTS = ("none", "random", "half_zero")
 KEYS = ("x_mean", "x_var", "y_mean", "y_var", "x_path", "y_path")
 
 
-def model_case(model, n, b):
-    return dict(next(c for c in CASES if c["model"] == model), N=n, B=b)
+LEVEL_MODELS = ("lg1d", "rw2d_theta", "ou_level")  # models whose cloud stays at a level: beta = 0.99, a random walk, gamma at the level
+LEVELS = (1e4, 1e6)
+LEVEL_SHAPES = ((1000, 3), (4100, 3))  # one ragged tile; five tiles with 4 particles in the last
+
+
+def model_case(model, n, b, level=0.0):
+    case = dict(next(c for c in CASES + LEVEL_CASES if c["model"] == model), N=n, B=b)
+    if model == "ou_level":
+        case["level"] = level
+    return case
 
 
 def _wsum(w, first, extra, dtype):
@@ -56,11 +64,12 @@ def forecast(spec, x, w, z, e=None):
 
 class Inputs:
     """One forecast call: a cloud one transition on from the model's initial law, weights, tapes - float64 values that are exact
-    in float32 (drawn in float32), so the float32 runs see the same numbers."""
+    in float32 (drawn in float32), so the float32 runs see the same numbers.  ``level``: the cloud shifted there (``ou_level``: its
+    ``gamma`` and initial law are at the level already)."""
 
-    def __init__(self, model, n, b, h, weights="random", seed=0):
-        self.model, self.n, self.b, self.h, self.weights = model, n, b, h, weights
-        self.case = model_case(model, n, b)
+    def __init__(self, model, n, b, h, weights="random", seed=0, level=0.0):
+        self.model, self.n, self.b, self.h, self.weights, self.level = model, n, b, h, weights, level
+        self.case = model_case(model, n, b, level)
         spec = build_spec(self.case, torch.float64)
         self.has_d, self.has_o = spec.dim > 0, spec.obs_dim > 0
         gen = torch.Generator().manual_seed(4000 + seed)
@@ -68,6 +77,8 @@ class Inputs:
         tail = (spec.dim,) if self.has_d else ()
         otail = (spec.obs_dim,) if self.has_o else ()
         x = M.propagate(spec, M.initial_sample(spec, rn(n, b, *tail)), rn(n, b, *tail))
+        if level and model != "ou_level":
+            x = x + level
         self.x = x.float().double()
         self.z, self.e = rn(h, n, b, *tail), rn(h, n, b, *otail)
         if weights == "none":
@@ -80,7 +91,7 @@ class Inputs:
             self.w = w.float().double()
 
     def __repr__(self):
-        return f"{self.model} {self.n}x{self.b} H={self.h} W={self.weights}"
+        return f"{self.model} {self.n}x{self.b} H={self.h} W={self.weights}" + (f" level={self.level:g}" if self.level else "")
 
     def reference(self, dtype=torch.float64):
         """The float64 oracle on these inputs with the parameters as a run in ``dtype`` holds them."""
@@ -101,6 +112,31 @@ def grid(models, dtype=torch.float64):
                     continue
                 for k, weights in enumerate(WEIGHTS):
                     yield Inputs(model, n, b, h, weights, seed=k)
+
+
+def level_grid(models=LEVEL_MODELS, levels=LEVELS):
+    """The calls of the tests at a level: every model, level, shape, horizon and kind of weights."""
+    for model in models:
+        for level in levels:
+            for n, b in LEVEL_SHAPES:
+                for h in HORIZONS:
+                    for k, weights in enumerate(WEIGHTS):
+                        yield Inputs(model, n, b, h, weights, seed=k, level=level)
+
+
+def relative_error(got, ref):
+    """``max |d| / |ref|`` (an entry whose reference is 0 must be met exactly: inf otherwise)"""
+    got, ref = got.double().cpu(), ref.double()
+    zero = ref == 0
+    if bool((got[zero] != 0).any()):
+        return float("inf")
+    return float(((got - ref).abs()[~zero] / ref.abs()[~zero]).max()) if bool((~zero).any()) else 0.0
+
+
+def level_errors(got, ref):
+    """(worst scaled error of the two means, worst error of the two variances RELATIVE TO THE VARIANCE, worst scaled error of the paths)"""
+    return (max(scaled_error(got[k], ref[k]) for k in ("x_mean", "y_mean")), max(relative_error(got[k], ref[k]) for k in ("x_var", "y_var")),
+            max(scaled_error(got[k], ref[k]) for k in KEYS[4:]))
 
 
 def scaled_error(got, ref):

@@ -106,6 +106,15 @@ def build_ssm_from_case(case, dtype, device):
         sigma = t([0.05 + 0.01 * i for i in range(b)])
         hidden = models.OrnsteinUhlenbeck(kappa, gamma, sigma, dt=1.0, initial=(t(0.0), t(0.1)))
         ssm = ts.LinearStateSpaceModel(hidden, (t(1.0), t(0.05)))
+    elif m == "ou_level":  # ou_batched at a level of 1e4 (oracle/cases.py: LEVEL_CASES)
+        from oracle.cases import LEVEL
+
+        level = float(case.get("level", LEVEL))
+        kappa = t([0.025 * (i + 1) for i in range(b)])
+        gamma = t([level + 0.1 * i for i in range(b)])
+        sigma = t([0.05 + 0.01 * i for i in range(b)])
+        hidden = models.OrnsteinUhlenbeck(kappa, gamma, sigma, dt=1.0, initial=(t(level), t(0.05)))
+        ssm = ts.LinearStateSpaceModel(hidden, (t(1.0), t(0.05)))
     else:
         raise KeyError(m)
     ssm.observe_every_step = int(case.get("observe_every_step", 1))

@@ -8,14 +8,15 @@ import pytest
 import torch
 
 from oracle import cpu_ref
-from oracle.cases import CASE_BY_NAME, CASES, CLUSTER_CASES, PARTIAL_NAN_CASES, build_spec
+from oracle.cases import CASE_BY_NAME, CASES, CLUSTER_CASES, LEVEL_CASES, PARTIAL_NAN_CASES, build_spec
 from tests.helpers import assert_close_nan_aware
 
 DT = {"f64": torch.float64, "f32": torch.float32}
 PARTIAL_PARAMS = [(c["name"], d) for c in PARTIAL_NAN_CASES for d in c["dtypes"]]
 PARAMS = [(c["name"], d) for c in CASES for d in c["dtypes"]]
 # (+ the reference's runs at column-cluster sizes, round 6: filtering arrays only)
-FILTER_PARAMS = PARAMS + [(c["name"], d) for c in CLUSTER_CASES for d in c["dtypes"]]
+# (+ the runs at a level of 1e4, oracle/cases.py: LEVEL_CASES)
+FILTER_PARAMS = PARAMS + [(c["name"], d) for c in CLUSTER_CASES + LEVEL_CASES for d in c["dtypes"]]
 
 
 def load(golden_dir, name, dt):
