@@ -203,15 +203,10 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
     ColParams<T, D> cp;
     ColConsts<T, D> cc;
     load_col_params<T, D>(a, b, run.t0, false, cp);
-    if constexpr (KIND >= 0) {
-        static_assert((D == 1) == (KIND != PF_HID_LORENZ63_EM), "specialised cluster kernels: built-in models");
-        md.hid_kind = KIND;
-        md.obs_kind = (KIND == PF_HID_VERHULST_EM) ? PF_OBS_SV : PF_OBS_LINEAR;
-        if constexpr (D == 1) md.obs_dim = 1;
-    }
+    fold_model_kind<KIND, D>(md);
     const T* const z_tape = (KIND >= 0) ? nullptr : a.z_tape;
     cc.prepare(md, cp);
-    if constexpr (KIND >= 0) __builtin_assume(cc.fast == (D == 1 && KIND != PF_HID_VERHULST_EM));
+    assume_folded_kind<KIND>(cc);
     auto y_row = [&](int t) { return a.y + ((int64_t)t * a.y_rows + (a.y_rows == 1 ? 0 : b)) * O; };
 
     // pivot of the weighted moments: the column's first particle, then (about) the previous state's mean - every member moves it
@@ -233,14 +228,8 @@ __global__ __launch_bounds__(PFK_TPB, (sizeof(T) == 4 && D == 1) ? (VEC == 4 ? 4
     // rw of the NEXT move (cp.yn / cc.ybn hold its observation): lw + first-stage weights when that move is a weighted APF move
     // log-sum-exp over a wave's chunk of VEC sanitised values per lane (-inf: no contribution; -inf when there is none)
     auto wave_lse = [&](const T (&v)[VEC]) -> T {
-        T m = v[0];
-#pragma unroll
-        for (int j = 1; j < VEC; ++j) m = v[j] > m ? v[j] : m;
-        const T mw = wave_max<T>(m);
-        T sm = T(0);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) sm += (v[j] == -Lim<T>::inf()) ? T(0) : pf_exp_w(v[j] - mw);
-        sm = wave_sum<T>(sm);
+        T mw, sm;
+        wave_lse_parts<T, VEC>(v, mw, sm);
         return (T)((double)mw + log_sum<T>((double)sm));
     };
     // aux_w: see `flat` in the loop below - the chunk's lse of a SISR move's own weights, published in the slot of sum e^2 when

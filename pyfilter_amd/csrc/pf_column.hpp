@@ -33,53 +33,7 @@ struct ColumnRun {
     uint32_t obs_bits[PFC_OBS_WORDS];  // bit s = step t0 + s weighs against y[t0 + s]
 };
 
-// Workgroup barrier for LDS exchanges ONLY: waits for this wave's outstanding LDS operations (lgkmcnt), not for its global
-// ones.  __syncthreads() carries a workgroup-scope fence, i.e. an `s_waitcnt vmcnt(0)` - it would make every step wait for
-// the result rows thread 0 has just stored (means / variances / log-likelihood: never read in this launch) and for the
-// next step's observation that was requested a step ahead precisely so that nobody waits for it.  A single-wave workgroup
-// needs no barrier at all (its LDS operations execute in order): a compiler fence.
-__device__ __forceinline__ void pfc_barrier(int nw) {
-    if (nw > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("" ::: "memory");
-}
-
-// exclusive scan of one double per thread across a workgroup of `nw` waves (1 .. 16); a single wave never touches LDS
-__device__ __forceinline__ double cb_scan_excl(double v, double* red, int nw, double& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const double incl = wave_scan_incl(v, lane);
-    if (nw == 1) {
-        total = lane_get(incl, 63);
-        return incl - v;
-    }
-    pfc_barrier(nw);
-    if (lane == 63) red[wid] = incl;
-    pfc_barrier(nw);
-    double off = 0.0, tot = 0.0;
-    for (int w = 0; w < nw; ++w) {
-        const double s = red[w];
-        if (w < wid) off += s;
-        tot += s;
-    }
-    total = tot;
-    return off + incl - v;
-}
-
-// log of a column sum / reciprocal of one, at the precision the filter's type needs: float filters take the hardware
-// log2 / rcp (their results are rounded to float anyway), double filters the exact forms (the parity path)
-template <typename T> __device__ __forceinline__ double log_sum(double s) {
-    if constexpr (sizeof(T) == 4) return (double)pf_log_g((float)s);
-    else return log(s);
-}
-template <typename T> __device__ __forceinline__ double inv_sum(double s) {
-    if constexpr (sizeof(T) == 4) {
-        double r = (double)__builtin_amdgcn_rcpf((float)s);
-        r = __builtin_fma(__builtin_fma(-s, r, 1.0), r, r);  // one Newton step: ~2^-46
-        return r;
-    } else {
-        return 1.0 / s;
-    }
-}
-
+// (pfc_barrier, cb_scan_excl, log_sum / inv_sum, wave_lse_parts and the KIND fold: pf_colwave.hpp, shared with pf_cluster.hpp)
 // TPB: the launch bound - 256 or 1024 threads per workgroup, each its own instantiation, so that the filters of <= 1024
 // particles are not register-limited by the bound the larger ones need (1024 threads: 128 VGPRs and, for D > 1, scratch)
 // USER: PF_HID_USER_AFFINE runs (the caller's (loc, scale) planes gathered at the ancestors) are their own instantiation -
@@ -180,18 +134,14 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
     ColParams<T, D> cp;
     ColConsts<T, D> cc;
     load_col_params<T, D>(a, b, run.t0, false, cp);
-    if constexpr (KIND >= 0) {  // (the host selects these instantiations for exactly such runs)
-        static_assert(!USER && (D == 1) == (KIND != PF_HID_LORENZ63_EM), "specialised column kernels: built-in models");
-        md.hid_kind = KIND;
-        md.obs_kind = (KIND == PF_HID_VERHULST_EM) ? PF_OBS_SV : PF_OBS_LINEAR;  // (Verhulst: the stochastic-volatility built-in)
-        if constexpr (D == 1) md.obs_dim = 1;
-    }
+    static_assert(KIND < 0 || !USER, "specialised column kernels: built-in models");
+    fold_model_kind<KIND, D>(md);
     const T* const z_tape = (KIND >= 0) ? nullptr : a.z_tape;  // (specialised runs draw their normals: Philox)
     cc.prepare(md, cp);
     if constexpr (USER) {  // one transition scale per column: the scalar closed forms around the caller's mean (ColConsts::prepare_user)
         if (a.user_scale_percol) cc.prepare_user(md, cp, a.user_scale[b]);
     }
-    if constexpr (KIND >= 0) __builtin_assume(cc.fast == (D == 1 && KIND != PF_HID_VERHULST_EM));
+    assume_folded_kind<KIND>(cc);
     auto y_row = [&](int t) { return a.y + ((int64_t)t * a.y_rows + (a.y_rows == 1 ? 0 : b)) * O; };
 
     // pivot of the weighted moments: the column's first particle, then (about) the previous state's mean
@@ -294,17 +244,10 @@ __global__ __launch_bounds__(TPB) void k_fused_column(FusedArgs<T> a, ColumnRun 
             if (dm == dm) piv[d] = (T)((double)piv[d] + dm);  // (a state without weight - NaN row - leaves the pivot where it was)
         }
     };
-    // log-sum-exp over the column of VEC sanitised values per lane (-inf: no contribution).  Off the common path: the
-    // log-likelihood terms of a column whose weights carry no information (below).  Two barriers; uses recA.
+    // log-sum-exp over the column of VEC sanitised values per lane: the log-likelihood terms of a flat column.  Two barriers; uses recA.
     auto column_lse = [&](const T (&v)[VEC]) -> double {
-        T m = v[0];
-#pragma unroll
-        for (int j = 1; j < VEC; ++j) m = v[j] > m ? v[j] : m;
-        const T mw = wave_max<T>(m);
-        T s = T(0);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) s += (v[j] == -Lim<T>::inf()) ? T(0) : pf_exp_w(v[j] - mw);
-        s = wave_sum<T>(s);
+        T mw, s;
+        wave_lse_parts<T, VEC>(v, mw, s);
         double M = (double)mw, S = (double)s;
         if (nw > 1) {
             if (lane == 0) {

@@ -182,6 +182,7 @@ enum { PQ_M1 = 0, PQ_S1 = 1, PQ_Q1 = 2, PQ_M2 = 3, PQ_S2 = 4, PQ_E = 5, PQ_MX = 
 
 #include "pf_search.hpp"
 #include "pf_fused.hpp"
+#include "pf_colwave.hpp"
 #include "pf_column.hpp"
 #include "pf_cluster.hpp"
 

@@ -34,11 +34,27 @@ def unit_of(recipe, name: str, work: str):
     raise SystemExit(f"no unit {name} in {recipe.ROOT}")
 
 
-def descriptors(unit, work: str):
-    cmd = ge.unit_command(unit, ["-save-temps"])
+def checkout(rev: str, tree: str):
+    """the library's sources and build recipe as of ``rev``, written under ``tree``"""
+    paths = subprocess.check_output(["git", "ls-tree", "-r", "--name-only", rev, "pyfilter_amd/csrc", "include", "__graft_entry__.py"],
+                                    cwd=ROOT, text=True).split()
+    for path in paths:
+        os.makedirs(os.path.dirname(os.path.join(tree, path)), exist_ok=True)
+        with open(os.path.join(tree, path), "wb") as f:
+            f.write(subprocess.check_output(["git", "show", f"{rev}:{path}"], cwd=ROOT))
+
+
+def gfx950_listing(unit, work: str, extra=()) -> str:
+    """the gfx950 assembly of a ``-save-temps`` build of one unit (``extra``: further flags)"""
+    cmd = ge.unit_command(unit, ["-save-temps"] + list(extra))
     subprocess.check_call(cmd["args"], cwd=work, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)  # (the temporaries land in cwd)
     stem = os.path.splitext(os.path.basename(unit[0]))[0]
-    text = open(os.path.join(work, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+    with open(os.path.join(work, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s")) as f:
+        return f.read()
+
+
+def descriptors(unit, work: str):
+    text = gfx950_listing(unit, work)
     out = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S):
         num = lambda key: int(re.search(r"\.amdhsa_" + key + r"\s+(\d+)", m.group(2)).group(1))  # noqa: E731
@@ -62,12 +78,7 @@ def main():
     old = None
     if rev:
         with tempfile.TemporaryDirectory() as tree, tempfile.TemporaryDirectory() as w2:
-            paths = subprocess.check_output(["git", "ls-tree", "-r", "--name-only", rev, "pyfilter_amd/csrc", "include", "__graft_entry__.py"],
-                                            cwd=ROOT, text=True).split()
-            for path in paths:
-                os.makedirs(os.path.dirname(os.path.join(tree, path)), exist_ok=True)
-                with open(os.path.join(tree, path), "wb") as f:
-                    f.write(subprocess.check_output(["git", "show", f"{rev}:{path}"], cwd=ROOT))
+            checkout(rev, tree)
             old = descriptors(unit_of(load_recipe(tree), unit, w2), w2)  # (that revision's sources with that revision's flags)
     names = demangle(sorted(set(new) | set(old or {})))
     fmt = lambda r: f"LDS {r[0]:6d} B  scratch {r[1]:4d} B  VGPRs {r[2]:3d}"  # noqa: E731
