@@ -209,6 +209,22 @@ int pf_forecast(const pf_model* model, int steps, const void* x, const void* W, 
                 void* x_mean, void* x_var, void* y_mean, void* y_var, void* x_path, void* y_path, void* ws, size_t ws_bytes,
                 int64_t N, int64_t B, int dtype, void* stream);
 
+/* Path score: the complete-data log-likelihood of smoothed trajectories and its gradient with respect to the parameter rows -
+ * the expression the reference differentiates with torch autograd for its gradient-based PMMH proposal (`_model_likelihood`,
+ * inference/batch/mcmc/proposals/gradient.py:9-32; particle/base.py:176-210) without its initial-state and prior terms, as one
+ * streaming pass.  paths (S,D,B,N): pf_smooth_ffbs' layout; y (S-1,y_rows,O) with y_rows in {1, B}: row t-1 observes state t.
+ *   value[b]   = 1/N sum_j sum_{t=1..S-1} [ log p(x_t^j | x_{t-1}^j) + log p(y_t | x_t^j) ]                       value (B)
+ *   grad[b][k] = d value[b] / d params[b][k], the row layout of pf_model.params (slots a kind never reads: 0)     grad (B,NP)
+ * Both outputs are float64 for either dtype, and the per-term arithmetic is double.  An observation row that is NaN in all its
+ * elements contributes no observation term (the filters skip it; the reference's expression would be NaN); a row NaN in only
+ * some elements makes value[b] and all of grad[b] NaN for the filters it belongs to.
+ * Built-in kinds of D, O <= 3: PF_HID_LINEAR_MAT, PF_HID_USER_AFFINE and larger shapes are PF_EUNSUPPORTED; S < 2, a y_rows that
+ * is neither 1 nor B and null pointers are PF_EINVAL.  ws: pf_path_score_workspace_bytes(N, B, S) bytes - the workgroups' partial
+ * sums, added by a second small kernel in a fixed order (no float atomics: a result is a function of inputs and shape). */
+int pf_path_score_workspace_bytes(int64_t N, int64_t B, int64_t S, size_t* bytes);
+int pf_path_score(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value, double* grad, void* ws,
+                  size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
+
 /* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
  * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
 int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,

@@ -1662,6 +1662,41 @@ extern "C" int pf_forecast(const pf_model* model, int steps, const void* x, cons
     });
 }
 
+// ---- path score (pf_score.hpp) ----------------------------------------------------------------------------------------------
+#include "pf_score.hpp"
+extern "C" int pf_path_score_workspace_bytes(int64_t N, int64_t B, int64_t S, size_t* bytes) {
+    if (!bytes || bad_shape(N, B) || S < 2 || S > INT32_MAX) return PF_EINVAL;
+    const ScorePlan p = score_plan(N, B, S);
+    *bytes = sizeof(double) * (size_t)PF_SCORE_Q * (size_t)B * (size_t)p.tiles * (size_t)p.chunks;
+    return PF_OK;
+}
+extern "C" int pf_path_score(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value, double* grad,
+                             void* ws, size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype, void* stream) {
+    if (!model || !model->params || !paths || !y || !value || !grad || !ws) return PF_EINVAL;
+    if (model->hid_kind == PF_HID_LINEAR_MAT || model->hid_kind == PF_HID_USER_AFFINE) return PF_EUNSUPPORTED;
+    int rc = check_model(model);  // (D or O above 3, an unknown kind: PF_EUNSUPPORTED)
+    if (rc) return rc;
+    if (S < 2 || S > INT32_MAX || bad_shape(N, B) || (y_rows != 1 && y_rows != B)) return PF_EINVAL;
+    size_t need = 0;
+    pf_path_score_workspace_bytes(N, B, S, &need);
+    if (ws_bytes < need) return PF_EWORKSPACE;
+    const ModelDesc md = to_desc(model);
+    const ScorePlan p = score_plan(N, B, S);
+    const int NP = 4 * model->dim + model->obs_dim * model->dim + 2 * model->obs_dim;
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_d3(model->dim, [&](auto d) {
+            hipLaunchKernelGGL((k_score_part<T, decltype(d)::value>), dim3((unsigned)p.tiles, (unsigned)B, (unsigned)p.chunks), dim3(PF_BLOCK), 0,
+                               st, md, (const T*)model->params, (const T*)paths, (const T*)y, (int)y_rows, (double*)ws, (int)S, p.len, N,
+                               (int)B);
+            hipLaunchKernelGGL(k_score_final, dim3(1 + NP, (unsigned)B), dim3(PF_BLOCK), 0, st, (const double*)ws, value, grad,
+                               p.tiles * p.chunks, N, (int)B);
+            return launch_status();
+        });
+    });
+}
+
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;

@@ -1029,11 +1029,13 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         the draw of state t given state t + 1) - ``None`` restores Philox."""
         self._ffbs_u = u
 
-    def smooth(self, states, method: str = "ffbs") -> torch.Tensor:
+    def smooth(self, states, method: str = "ffbs", generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """Smoothed trajectories ``(S, N, [B], [D])`` from recorded states: ``"fl"`` - every particle of the last state
         traced back along its ancestors (:136-152); ``"ffbs"`` - forward filtering, backward simulation (:105-134).  Both are
         one kernel launch over the state history for built-in models on the GPU; ``"ffbs"`` with user callables evaluates
-        the reference's (N, N) logits with torch ops."""
+        the reference's (N, N) logits with torch ops.  ``generator`` (on the states' device): where ``"ffbs"`` resamples the last
+        state with this package's ``systematic`` / ``multinomial`` the draw comes from it instead of torch's global generator
+        (the backward draws are keyed by the filter's seed already)."""
         states = list(states)
         low = method.lower()
         if low not in ("ffbs", "fl"):
@@ -1048,7 +1050,13 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             return torch.stack([ops.from_soa(o, self._batched, self._has_event) for o in out.unbind(0)], 0)
         # ffbs: the last state resampled by the filter's resampler, then the backward draws
         w_last = states[-1].weights
-        idx = self._resampler(w_last)
+        if generator is not None and self._resampler is systematic:
+            nb = w_last.shape[1] if w_last.dim() > 1 else 1
+            idx = systematic(w_last, u=torch.rand(nb, generator=generator, device=w_last.device, dtype=w_last.dtype))
+        elif generator is not None and self._resampler is multinomial:
+            idx = multinomial(w_last, seed=generator.initial_seed() & _M64)  # (keyed by the generator's seed: no device read)
+        else:
+            idx = self._resampler(w_last)
         from ..utils import batched_gather
 
         start = batched_gather(x_last, idx, 0)
@@ -1063,6 +1071,32 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
                                   u, self._next_draw_seed())
             return torch.stack([ops.from_soa(o, self._batched, self._has_event) for o in out.unbind(0)], 0)
         return self._ffbs_with_callables(states, start)
+
+    def path_score(self, paths: torch.Tensor, y: torch.Tensor, theta=None, route: str = "auto"):
+        """The complete-data log-likelihood of the trajectories ``paths (S, N, [B], [D])`` - as ``smooth`` returns them - given the
+        observations ``y (S - 1, [By], [O])`` (row ``t - 1`` observes state ``t``; ``By`` in {1, B}), per filter: ``([B],)``
+
+            initial_distribution.log_prob(x_0).mean(0) + (log p(x_t | x_{t-1}) + log p(y_t | x_t)).sum(0).mean(0)
+
+        the reference's ``_model_likelihood`` without its prior term (``proposals/gradient.py:9-32``).  Over smoothed
+        trajectories its gradient estimates the score of the marginal likelihood (Fisher's identity): the drift of
+        ``GradientBasedProposal``, the E-step statistic of particle EM, the input of a gradient optimiser.
+
+        ``theta``: a mapping name -> tensor of the constrained values the model builder indexes.  Then ``(value, {name: d value /
+        d theta[name]})`` is returned: the tensors are cloned as leaves and the model is rebuilt from them, so the filter's own
+        model and parameters stay untouched.
+
+        ``route="auto"``: a built-in model of up to three state / observation components on a GPU takes one launch of
+        ``pf_path_score`` (float64 outputs) and a vector-Jacobian product through the builder and ``pack_params``; anything else -
+        user callables, ``LinearModel``, larger shapes, CPU tensors - torch autograd of the whole expression, which
+        ``route="torch"`` forces.  ``route="kernel"`` raises where the kernel does not apply.  An observation that is NaN in all
+        its elements contributes no observation term (``filters/particle/score.py``)."""
+        from .score import path_score
+
+        assert self._model is not None, "Model has not been initialized!"
+        if int(self._model.observe_every_step) != 1:
+            raise NotImplementedError("path_score: the expression assumes observe_every_step = 1")
+        return path_score(self, paths, y, theta, route)
 
     def _ffbs_with_callables(self, states, start):
         """User-defined models: the reference's own evaluation (an (N, N, [B]) logits tensor per step) with torch ops."""

@@ -62,15 +62,18 @@ def normalized_weights(log_w: torch.Tensor) -> torch.Tensor:
     return torch.softmax(lw - lw.max(dim=0, keepdim=True)[0], dim=0)
 
 
-def kernel_applies(ctx, x: torch.Tensor) -> bool:
-    """A built-in kind of the stand-alone model kernels with ``D, O <= 3``, on a GPU."""
-    if ctx is None or not x.is_cuda:
+def kind_has_kernel(k, x: torch.Tensor) -> bool:
+    """A built-in kind of the stand-alone model kernels with ``D, O <= 3``, tensors on a GPU (``pf_forecast``, ``pf_path_score``)."""
+    if k is None or not x.is_cuda:
         return False
-    k = ctx.kind
     return not k.is_user and k.hid_kind != L.HID_LINEAR_MAT and k.dim <= L.MAX_D and k.obs_dim is not None and k.obs_dim <= L.MAX_O
 
 
-def _tape_soa(t: Optional[torch.Tensor], like: torch.Tensor, batched: bool, has_event: bool) -> Optional[torch.Tensor]:
+def kernel_applies(ctx, x: torch.Tensor) -> bool:
+    return ctx is not None and kind_has_kernel(ctx.kind, x)
+
+
+def tape_soa(t: Optional[torch.Tensor], like: torch.Tensor, batched: bool, has_event: bool) -> Optional[torch.Tensor]:
     """``(steps, N, [B], [K])`` -> the kernel's ``(steps, K, B, N)``."""
     if t is None:
         return None
@@ -97,7 +100,7 @@ def kernel_forecast(ctx, obs_event: bool, x: TimeseriesState, w: Optional[torch.
     """``pf_forecast`` on the reference-layout state ``x`` and normalised weights ``w (N, [B])``."""
     soa = ops.to_soa(x.value, ctx.batched, ctx.has_event)
     xm, xv, ym, yv, xp, yp = ops.forecast_soa(ctx.kind, ctx.params, steps, soa, None if w is None else ops.to_cols(w),
-                                              _tape_soa(z, soa, ctx.batched, ctx.has_event), _tape_soa(e, soa, ctx.batched, obs_event),
+                                              tape_soa(z, soa, ctx.batched, ctx.has_event), tape_soa(e, soa, ctx.batched, obs_event),
                                               seed, paths)
 
     def shaped(m, event):

@@ -83,6 +83,59 @@ class RandomWalk:
         latest.base_dist.scale.copy_(torch.where(m, candidate.base_dist.scale, latest.base_dist.scale))
 
 
+class GradientBasedProposal(RandomWalk):
+    """The gradient-informed proposal of PMMH (``proposals/gradient.py:35-97``): theta* ~ N(u + eps grad S(theta), scale) with
+    ``eps = scale^2 / 2``, ``u`` the chain's current unconstrained value and ``S`` the log-likelihood plus the log prior.
+    ``grad S`` is estimated by Fisher's identity: the filter's recorded states are smoothed (``method``: ``"ffbs"`` or ``"fl"``),
+    the complete-data log-likelihood of the trajectories is differentiated (``ParticleFilter.path_score``: one HIP launch for
+    the built-in models) and the gradient of ``theta.eval_priors(constrained=False)`` is added.
+
+    As in the reference (``gradient.py:88-97``) the gradient is taken with respect to the CONSTRAINED values and added to the
+    UNCONSTRAINED ones: for a parameter whose bijection is not the identity the drift is not the gradient in the space the
+    kernel lives in.  It is a drift all the same - the Metropolis-Hastings correction of ``run_pmmh`` evaluates the forward and
+    the reverse kernel at their own centres, so the chain targets the posterior whatever the drift.  A chain whose gradient is
+    not finite (a filter that lost all its weight) gets no drift: the random walk's kernel.
+
+    The filter must record all its states (``record_states=True``), as the reference asserts.  ``exchange`` is ``RandomWalk``'s:
+    after an accepted move the chain takes over the kernel built at the accepted value."""
+
+    def __init__(self, scale=1e-2, method: str = "ffbs", use_second_order: bool = False):
+        if use_second_order:
+            raise NotImplementedError("Currently does not support `use_second_order`!")
+        super().__init__(scale)
+        self._eps = scale ** 2.0 / 2.0
+        self._method = method
+
+    def build(self, theta, state, filter_, y):
+        states = state.filter_state.states
+        if filter_.record_states is not True or len(states) < 2:
+            raise ValueError("GradientBasedProposal smooths the filter's recorded states: build the filter with `record_states=True`")
+        # (smoothing resamples the last state: the draw comes from a generator seeded by the filter's own seed and draw counter,
+        # not from torch's global one, so that a PMMH run stays a function of its seeds)
+        if isinstance(filter_, ParticleFilter):
+            gen = torch.Generator(device=states[-1].timeseries_state.value.device)
+            gen.manual_seed((filter_._seed * 0x9E3779B1 + filter_._draws) & 0x7FFFFFFFFFFFFFFF)
+            paths = filter_.smooth(states, self._method, generator=gen)
+        else:
+            paths = filter_.smooth(states, self._method)
+        names = theta.names()
+        _, grads = filter_.path_score(paths, y, theta={n: theta[n] for n in names})
+        u = theta.stack_parameters(constrained=False)
+        b = u.shape[0]
+        cols = []
+        for n in names:
+            prior, leaf = theta.priors[n], theta[n].detach().clone().requires_grad_(True)
+            with torch.enable_grad():
+                prior.eval_prior(leaf, constrained=False).sum().backward()
+            cols.append((grads[n].to(u.dtype) + leaf.grad).reshape(b, -1))
+        g = torch.cat(cols, dim=-1)
+        if g.shape != u.shape:
+            raise NotImplementedError("GradientBasedProposal: a prior whose bijection changes the number of elements")
+        loc = u + self._eps * torch.nan_to_num(g, nan=0.0, posinf=0.0, neginf=0.0)
+        scale = torch.as_tensor(self._scale, device=loc.device, dtype=loc.dtype).expand_as(loc).clone()
+        return Independent(Normal(loc, scale, validate_args=False), 1, validate_args=False)
+
+
 class ThetaDraws:
     """Source of the theta-level random numbers of SMC^2 / PMMH (the reference takes them from torch's global generator:
     ``kernels/mh.py:53`` the resampling uniform, ``mcmc/utils.py:48`` the proposal's standard normals, ``:69`` the

@@ -156,6 +156,9 @@ def exchange_filters(dst_t: torch.Tensor, src_t: torch.Tensor, mask: torch.Tenso
                                          L.stream_ptr()), "pf_columns_exchange")
     out = rebuild(dst)
     if out.data_ptr() != dst_t.data_ptr():  # dst_t was in a foreign layout: write the result back into it
+        # (a broadcast view - the initial state's ancestors are an expanded arange - cannot be written: the callers keep what is returned)
+        if any(st == 0 and sz > 1 for st, sz in zip(dst_t.stride(), dst_t.shape)):
+            return out
         dst_t.copy_(out)
         return dst_t
     return out
@@ -392,6 +395,34 @@ def forecast_soa(kind, params, steps: int, x: torch.Tensor, W: Optional[torch.Te
         "pf_forecast",
     )
     return (*moments, x_path, y_path)
+
+
+def path_score(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The complete-data log-likelihood of the trajectories ``paths_soa (S, D, B, N)`` (``smooth_ffbs``' layout) under a built-in
+    model and its gradient with respect to the parameter rows ``params (B, NP)``, in one streaming launch (pf_path_score):
+    ``(value (B,), grad_rows (B, NP))``, both float64.  ``y (S - 1, [By], [O])`` with ``By`` in {1, B}: row ``t - 1`` observes state
+    ``t``; an all-NaN row contributes no observation term."""
+    L.require_gpu(paths_soa, y, params)
+    s, d, b, n = paths_soa.shape
+    o = int(kind.obs_dim)
+    dt, dev = paths_soa.dtype, paths_soa.device
+    assert paths_soa.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
+    if int(kind.dim) != d or params.shape[1] != 4 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+        raise L.PfAmdError(f"path_score: paths {tuple(paths_soa.shape)} / rows {tuple(params.shape)} do not match the model kind")
+    yy = y.to(device=dev, dtype=dt).reshape(s - 1, -1, o).contiguous() if s >= 2 else torch.zeros((1, 1, o), dtype=dt, device=dev)
+    rows = yy.shape[1]
+    if rows not in (1, b):
+        raise L.PfAmdError(f"observations of shape {tuple(y.shape)} do not broadcast against batch {b}")
+    value = torch.empty(b, dtype=torch.float64, device=dev)
+    grad = torch.empty((b, params.shape[1]), dtype=torch.float64, device=dev)
+    nbytes = C.c_size_t(0)
+    if s >= 2:  # (otherwise pf_path_score itself refuses the call)
+        L.check(L.load().pf_path_score_workspace_bytes(n, b, s, C.byref(nbytes)), "pf_path_score_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=dev)
+    mod = make_model_struct(kind, params)
+    L.check(L.load().pf_path_score(C.byref(mod), paths_soa.data_ptr(), yy.data_ptr(), rows, value.data_ptr(), grad.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), s, n, b, L.dtype_code(dt), L.stream_ptr()), "pf_path_score")
+    return value, grad
 
 
 def initial_sample_soa(m0, s0, n: int, b: int, d: int, dtype, device, seed: int, z: Optional[torch.Tensor] = None):
