@@ -105,6 +105,8 @@ def get_filter_mean_and_variance(values: torch.Tensor, weights: torch.Tensor, ha
 # --------------------------------------------------------------------------------------------------------------
 # proposals
 # --------------------------------------------------------------------------------------------------------------
+# (``HID_LINEAR_MAT`` specs run through the same four functions, with per-filter parameters ``(B, D, D)`` / ``(B, D)`` / ``(B, O, D)`` /
+# ``(B, O)`` and ``y`` of ``(O,)`` or ``(B, O)``: ``tests/linmat_cases.py``)
 def bootstrap_sample_and_weight(spec, y, x, z):
     """proposals/bootstrap.py:10-14."""
     new_x = M.propagate(spec, x, z)

@@ -13,6 +13,8 @@ README / notebooks / tests:
 * ``HID_VERHULST_EM``: ``v' = v + kappa*(gamma-v)*v*dt + sigma*v*eps`` examples/stochastic-volatility.ipynb (ts.models.Verhulst)
 * ``HID_LORENZ63_EM``: Lorenz-63 drift, Euler-Maruyama                examples/lorenz.ipynb (``f``), eps ~ N(0, sqrt(dt)) iid per dim
 * ``HID_OU``         : exact OU discretisation                        tests/inference/models.py:12-19
+* ``HID_LINEAR_MAT`` : ``x' = b + A x + s*eps``, full ``D x D`` matrix     LinearModel (timeseries/models.py): an AffineProcess whose
+                                                                      mean is the matrix product, scale constant per filter
 * ``OBS_LINEAR``     : ``y ~ N(b + A x, s)``                          LinearStateSpaceModel, proposals/linear.py:48
 * ``OBS_SV``         : ``y ~ N(mu, scale=x)``                         stochastic-volatility.ipynb ``build_obs`` at skew=0, kurt=1
 
@@ -25,6 +27,7 @@ import math
 import torch
 
 HID_LINEAR, HID_SINE_EM, HID_VERHULST_EM, HID_LORENZ63_EM, HID_OU = 0, 1, 2, 3, 4
+HID_LINEAR_MAT = 6  # (the library's PF_HID_LINEAR_MAT; 5 is its user-defined affine process, which has no closed form here)
 OBS_LINEAR, OBS_SV = 0, 1
 
 HIDDEN_NAMES = {
@@ -33,6 +36,7 @@ HIDDEN_NAMES = {
     HID_VERHULST_EM: "verhulst_em",
     HID_LORENZ63_EM: "lorenz63_em",
     HID_OU: "ou",
+    HID_LINEAR_MAT: "linear_mat",
 }
 
 
@@ -48,7 +52,8 @@ class ModelSpec:
         hidden: one of ``HID_*``.
         hidden_params: tuple of parameters (see table above).  ``HID_LINEAR``: (alpha, beta, sigma) each scalar,
             ``(B,)`` or - for D>0 - ``(D,)``;  ``HID_SINE_EM``: (gamma, sigma); ``HID_VERHULST_EM``: (kappa, gamma,
-            sigma); ``HID_LORENZ63_EM``: (s, r, b, sigma); ``HID_OU``: (kappa, gamma, sigma).
+            sigma); ``HID_LORENZ63_EM``: (s, r, b, sigma); ``HID_OU``: (kappa, gamma, sigma);
+            ``HID_LINEAR_MAT``: (A, b, s) with ``A`` ``(D, D)`` or ``(B, D, D)``, ``b`` and ``s`` ``(D,)`` or ``(B, D)``.
         dim: 0 for a scalar state (no trailing dim), else D.
         dt: step for the Euler-Maruyama kinds / OU (ignored by ``HID_LINEAR``).
         init: (mean, scale) of the Gaussian initial distribution; scalars or ``(D,)``.
@@ -100,6 +105,9 @@ def mean_scale(spec: ModelSpec, x: torch.Tensor):
         e = torch.exp(-kappa * dt)
         loc = gamma + (x - gamma) * e
         scale = sigma * torch.sqrt((1.0 - torch.exp(-2.0 * kappa * dt)) / (2.0 * kappa))
+    elif k == HID_LINEAR_MAT:
+        a, b, s = p
+        loc, scale = b + (a @ x.unsqueeze(-1)).squeeze(-1), s
     else:
         raise NotImplementedError(k)
 
