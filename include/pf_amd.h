@@ -62,8 +62,9 @@ extern "C" {
                               * Its parameter row is NOT the hp layout below:
                               *   [ A[D x D] row-major | b[D] | s[D] | A_obs[O x D] row-major | b_obs[O] | s_obs[O] ]
                               *   NP = D*D + 2*D + O*D + 2*O
-                              * Stand-alone model kernels only (pf_sample_and_weight, pf_pre_weight): pf_filter_run and
-                              * pf_smooth_ffbs refuse it (PF_EUNSUPPORTED). */
+                              * Stand-alone model kernels only (pf_sample_and_weight, pf_pre_weight): pf_filter_run,
+                              * pf_smooth_ffbs and pf_path_score refuse it (PF_EUNSUPPORTED); its backward simulation and its path
+                              * score are entry points of their own, pf_smooth_ffbs_linear and pf_path_score_linear. */
 /* observation kinds */
 #define PF_OBS_LINEAR 0 /* y ~ N(b + A x, s)   (LinearStateSpaceModel; proposals/linear.py:48) */
 #define PF_OBS_SV 1     /* y ~ N(mu, scale = x)                                                 */
@@ -224,6 +225,19 @@ int pf_forecast(const pf_model* model, int steps, const void* x, const void* W, 
 int pf_path_score_workspace_bytes(int64_t N, int64_t B, int64_t S, size_t* bytes);
 int pf_path_score(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value, double* grad, void* ws,
                   size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
+
+/* pf_path_score for PF_HID_LINEAR_MAT under PF_OBS_LINEAR, 1 <= D, O <= 8 (`_model_likelihood`, proposals/gradient.py:9-32, for
+ * stochproc's LinearModel): the same sums, conventions and layouts, with the gradient in that kind's row layout
+ *   grad (B, NP) = d value / d [ A[D x D] | b[D] | s[D] | A_obs[O x D] | b_obs[O] | s_obs[O] ],  NP = D*D + 2*D + O*D + 2*O
+ *   e_d = (x_{t,d} - b_d - sum_k A_dk x_{t-1,k}) / s_d:   dA_dk = e_d x_{t-1,k} / s_d   db_d = e_d / s_d   ds_d = (e_d^2 - 1) / s_d
+ *   r_o = y_o - bo_o - sum_d Ao_od x_{t,d}:   dAo_od = r_o x_{t,d} / so_o^2   dbo_o = r_o / so_o^2   dso_o = (r_o^2 / so_o^2 - 1) / so_o
+ * A workgroup accumulates a group of output rows (NP is up to 160 slots: too many for one thread's registers) and re-reads the
+ * path planes; the partial sums are added by a second kernel in a fixed order.  Any other kind, PF_OBS_SV and D or O outside
+ * 1 .. 8 are PF_EUNSUPPORTED; S < 2, N or B < 1, a y_rows that is neither 1 nor B and null pointers are PF_EINVAL - all before any
+ * launch: the outputs are untouched.  ws: pf_path_score_linear_workspace_bytes(N, B, S, D, O) bytes. */
+int pf_path_score_linear_workspace_bytes(int64_t N, int64_t B, int64_t S, int64_t D, int64_t O, size_t* bytes);
+int pf_path_score_linear(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value, double* grad,
+                         void* ws, size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
 
 /* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
  * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
@@ -534,6 +548,14 @@ int pf_smooth_fixed_lag(const void* x_hist, const int32_t* anc_hist, void* out, 
 int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const void* logw_hist, const void* x_last, const void* u,
                    uint64_t seed, void* out, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
 
+/* method "ffbs" (_do_sample_ffbs, particle/base.py:105-134) for PF_HID_LINEAR_MAT (D = model->dim in 1 .. 8, under PF_OBS_LINEAR
+ * with O in 1 .. 8): pf_smooth_ffbs' contract, layouts, tape and Philox keys with the candidate of this kind,
+ * log p(out[t+1][j] | x[t][i]) = -sum_d (out[t+1][j][d] - b_d - sum_k A_dk x[t][i][k])^2 / (2 s_d^2) + a constant of the filter -
+ * O(N S) memory where the reference's evaluation holds an (N, N, B, D) tensor per step.  Any other kind or shape:
+ * PF_EUNSUPPORTED; S < 1, N or B < 1 and null pointers (u excepted): PF_EINVAL - before any launch: `out` is untouched. */
+int pf_smooth_ffbs_linear(const pf_model* model, const void* x_hist, const void* logw_hist, const void* x_last, const void* u,
+                          uint64_t seed, void* out, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------ *
  * test support (no reference counterpart): lets a parity test feed the oracle the very draws a *production* run used
  * ------------------------------------------------------------------------------------------------------------ */
@@ -545,6 +567,7 @@ int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_steps, void* 
 
 /* The step-kernel instantiations the calling thread's most recent pf_filter_run launches selected, oldest first:
  * out[i] = { step, sizeof(T), D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI } (10 int32 per record, the last 2048 are kept).
+ * pf_smooth_ffbs_linear and pf_path_score_linear leave a record of their own per call: SPEC = 20 and 21, step 0, sizeof(T), D.
  * Returns the number of records written (>= 0) or a negative PF_E* code. */
 int pf_debug_launch_trace(int32_t* out, int max_records);
 /* The same with `fields` (1 .. 11) int32 per record: field 10 = the launch took the one-column leaf of the step kernel. */

@@ -36,6 +36,7 @@ EXPORTS = (
     "pf_theta_accept", "pf_theta_path", "pf_theta_resample", "pf_initial_sample_cols", "pf_theta_step", "pf_host_alloc",
     "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply", "pf_nested_sample_and_weight",
     "pf_forecast", "pf_forecast_workspace_bytes", "pf_path_score", "pf_path_score_workspace_bytes",
+    "pf_path_score_linear", "pf_path_score_linear_workspace_bytes", "pf_smooth_ffbs_linear",
 )
 
 
@@ -134,6 +135,8 @@ def load() -> C.CDLL:
     lib.pf_forecast.argtypes = [C.POINTER(PfModel), i32, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i32, vp]
     lib.pf_path_score_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     lib.pf_path_score.argtypes = [C.POINTER(PfModel), vp, vp, i64, vp, vp, vp, sz, i64, i64, i64, i32, vp]
+    lib.pf_path_score_linear_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, C.POINTER(sz)]
+    lib.pf_path_score_linear.argtypes = [C.POINTER(PfModel), vp, vp, i64, vp, vp, vp, sz, i64, i64, i64, i32, vp]
     lib.pf_initial_sample.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u64, vp, i64, i64, i64, i32, vp]
     lib.pf_filter_run.argtypes = [C.POINTER(PfFilterArgs), i64, i64, i32, vp]
     lib.pf_filter_run_timed.argtypes = [C.POINTER(PfFilterArgs), i64, i64, i32, vp, C.POINTER(C.c_float)]
@@ -142,6 +145,7 @@ def load() -> C.CDLL:
     lib.pf_filter_graph_destroy.argtypes = [vp]
     lib.pf_smooth_fixed_lag.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, vp]
     lib.pf_smooth_ffbs.argtypes = [C.POINTER(PfModel), vp, vp, vp, vp, u64, vp, i64, i64, i64, i32, vp]
+    lib.pf_smooth_ffbs_linear.argtypes = [C.POINTER(PfModel), vp, vp, vp, vp, u64, vp, i64, i64, i64, i32, vp]
     lib.pf_observed_flags.argtypes = [vp, i64, i64, i32, vp, vp]
     lib.pf_theta_ess.argtypes = [vp, i64, i64, i32, vp, vp]
     lib.pf_theta_path.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, u64, vp, vp]

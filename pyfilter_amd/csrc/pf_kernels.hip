@@ -1697,6 +1697,51 @@ extern "C" int pf_path_score(const pf_model* model, const void* paths, const voi
     });
 }
 
+// ---- PF_HID_LINEAR_MAT after the filter (pf_linear_smooth.hpp) -------------------------------------------------------------
+#include "pf_linear_smooth.hpp"
+// the one model these entry points serve: PF_HID_LINEAR_MAT under PF_OBS_LINEAR with 1 <= D, O <= 8
+static inline int check_linmat(const pf_model* m) {
+    if (!m || !m->params) return PF_EINVAL;
+    if (m->hid_kind != PF_HID_LINEAR_MAT) return PF_EUNSUPPORTED;
+    return check_model(m);
+}
+extern "C" int pf_path_score_linear_workspace_bytes(int64_t N, int64_t B, int64_t S, int64_t D, int64_t O, size_t* bytes) {
+    if (!bytes || bad_shape(N, B) || S < 2 || S > INT32_MAX) return PF_EINVAL;
+    if (D < 1 || D > PF_LIN_MAXD || O < 1 || O > PF_LIN_MAXO) return PF_EUNSUPPORTED;
+    const ScorePlan p = score_plan(N, B, S);
+    const size_t groups = (size_t)(lscore_groups((int)D) + lscore_groups((int)O));
+    *bytes = sizeof(double) * groups * (size_t)lscore_q((int)D) * (size_t)B * (size_t)p.tiles * (size_t)p.chunks;
+    return PF_OK;
+}
+extern "C" int pf_path_score_linear(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value,
+                                    double* grad, void* ws, size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype,
+                                    void* stream) {
+    if (!model || !model->params || !paths || !y || !value || !grad || !ws) return PF_EINVAL;
+    int rc = check_linmat(model);
+    if (rc) return rc;
+    if (S < 2 || S > INT32_MAX || bad_shape(N, B) || (y_rows != 1 && y_rows != B)) return PF_EINVAL;
+    const int D = model->dim, O = model->obs_dim;
+    size_t need = 0;
+    pf_path_score_linear_workspace_bytes(N, B, S, D, O, &need);
+    if (ws_bytes < need) return PF_EWORKSPACE;
+    const ScorePlan p = score_plan(N, B, S);
+    const int groups = lscore_groups(D) + lscore_groups(O);
+    const int NP = D * D + 2 * D + O * D + 2 * O;
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_d8(D, [&](auto d) {
+            trace_launch(0, (int)sizeof(T), D, 1, 0, 0, 0, PF_TRACE_SCORE_LINEAR, 0, 0);
+            hipLaunchKernelGGL((k_score_linmat_part<T, decltype(d)::value>), dim3((unsigned)p.tiles, (unsigned)B, (unsigned)(p.chunks * groups)),
+                               dim3(PF_BLOCK), 0, st, (const T*)model->params, O, (const T*)paths, (const T*)y, (int)y_rows, (double*)ws,
+                               (int)S, p.len, groups, N, (int)B);
+            hipLaunchKernelGGL(k_score_linmat_final, dim3(1 + NP, (unsigned)B), dim3(PF_BLOCK), 0, st, (const double*)ws, value, grad, D, O,
+                               p.tiles * p.chunks, N, (int)B);
+            return launch_status();
+        });
+    });
+}
+
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;
@@ -1970,6 +2015,25 @@ extern "C" int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const v
             using T = decltype(t);
             hipLaunchKernelGGL((k_ffbs<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params, (const T*)x_hist,
                                (const T*)logw_hist, (const T*)x_last, (const T*)u, seed, (T*)out, S, N, (int)B);
+            return launch_status();
+        });
+    });
+}
+
+extern "C" int pf_smooth_ffbs_linear(const pf_model* model, const void* x_hist, const void* logw_hist, const void* x_last,
+                                     const void* u, uint64_t seed, void* out, int64_t S, int64_t N, int64_t B, int dtype,
+                                     void* stream) {
+    if (!model || !x_hist || !logw_hist || !x_last || !out || S < 1 || bad_shape(N, B)) return PF_EINVAL;
+    int rc = check_linmat(model);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((N + PF_BLOCK - 1) / PF_BLOCK), (int)B);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        return with_d8(model->dim, [&](auto d) {
+            using T = decltype(t);
+            trace_launch(0, (int)sizeof(T), model->dim, 1, 0, 0, 0, PF_TRACE_FFBS_LINEAR, 0, 0);
+            hipLaunchKernelGGL((k_ffbs_linmat<T, decltype(d)::value>), grid, dim3(PF_BLOCK), 0, st, (const T*)model->params, model->obs_dim,
+                               (const T*)x_hist, (const T*)logw_hist, (const T*)x_last, (const T*)u, seed, (T*)out, S, N, (int)B);
             return launch_status();
         });
     });

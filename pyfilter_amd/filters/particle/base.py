@@ -1029,17 +1029,31 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         the draw of state t given state t + 1) - ``None`` restores Philox."""
         self._ffbs_u = u
 
-    def smooth(self, states, method: str = "ffbs", generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    def smooth(self, states, method: str = "ffbs", generator: Optional[torch.Generator] = None, route: str = "auto") -> torch.Tensor:
         """Smoothed trajectories ``(S, N, [B], [D])`` from recorded states: ``"fl"`` - every particle of the last state
         traced back along its ancestors (:136-152); ``"ffbs"`` - forward filtering, backward simulation (:105-134).  Both are
         one kernel launch over the state history for built-in models on the GPU; ``"ffbs"`` with user callables evaluates
         the reference's (N, N) logits with torch ops.  ``generator`` (on the states' device): where ``"ffbs"`` resamples the last
         state with this package's ``systematic`` / ``multinomial`` the draw comes from it instead of torch's global generator
-        (the backward draws are keyed by the filter's seed already)."""
+        (the backward draws are keyed by the filter's seed already).
+
+        ``route`` chooses how ``"ffbs"`` makes its backward draws (``"fl"`` ignores it):
+
+        * ``"auto"``: built-in kinds on a GPU take the kernel (``pf_smooth_ffbs``: Philox draws keyed by the filter's seed, or
+          the tape of ``set_smoothing_tape``); ``LinearModel`` and user callables take the torch logits with torch's
+          generator.  The matrix kind stays there although it has a kernel: a script that seeds torch and smooths a
+          ``LinearModel`` keeps the trajectories it had before that kernel existed.
+        * ``"kernel"``: the Philox / tape kernel where one exists - the built-in kinds and ``LinearModel`` (``D <= 8``, under
+          a linear-Gaussian observation) on a GPU, the latter through ``pf_smooth_ffbs_linear``: O(N S) memory where the
+          logits route holds an ``(N, N, [B], D)`` tensor per step.  ``PfAmdError`` where there is none (user callables, CPU
+          tensors).
+        * ``"torch"``: the logits route for any model."""
         states = list(states)
         low = method.lower()
         if low not in ("ffbs", "fl"):
             raise NotImplementedError(f"Currently do not support '{method}'!")
+        if route not in ("auto", "kernel", "torch"):
+            raise ValueError(f"smooth: route must be one of ('auto', 'kernel', 'torch'), got {route!r}")
         x_last = states[-1].timeseries_state.value
         on_gpu = x_last.is_cuda
         if low == "fl":
@@ -1048,6 +1062,12 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             x_hist, _, anc_hist = self._history(states)
             out = ops.smooth_fixed_lag(x_hist, anc_hist)
             return torch.stack([ops.from_soa(o, self._batched, self._has_event) for o in out.unbind(0)], 0)
+        ctx = self._ensure_context()
+        has_kernel = route != "torch" and ctx is not None and on_gpu and not ctx.kind.is_user
+        matrix = has_kernel and ctx.kind.hid_kind == L.HID_LINEAR_MAT
+        if route == "kernel" and not has_kernel:
+            raise L.PfAmdError("smooth: no backward-simulation kernel for this model / device (built-in kinds and LinearModel "
+                               "with D, O <= 8 under a linear-Gaussian observation, states on a GPU)")
         # ffbs: the last state resampled by the filter's resampler, then the backward draws
         w_last = states[-1].weights
         if generator is not None and self._resampler is systematic:
@@ -1060,15 +1080,14 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         from ..utils import batched_gather
 
         start = batched_gather(x_last, idx, 0)
-        ctx = self._ensure_context()
-        if ctx is not None and on_gpu and not ctx.kind.is_user and ctx.kind.hid_kind != L.HID_LINEAR_MAT:
+        if has_kernel and (route == "kernel" or not matrix):
             x_hist, w_hist, _ = self._history(states)
             u = self._ffbs_u
             if u is not None:
                 s1 = len(states) - 1
                 u = u.to(device=x_hist.device, dtype=x_hist.dtype).reshape(s1, x_hist.shape[3], x_hist.shape[2]).permute(0, 2, 1).contiguous()
-            out = ops.smooth_ffbs(ctx.kind, ctx.params, x_hist, w_hist, ops.to_soa(start, self._batched, self._has_event),
-                                  u, self._next_draw_seed())
+            run = ops.smooth_ffbs_linear if matrix else ops.smooth_ffbs
+            out = run(ctx.kind, ctx.params, x_hist, w_hist, ops.to_soa(start, self._batched, self._has_event), u, self._next_draw_seed())
             return torch.stack([ops.from_soa(o, self._batched, self._has_event) for o in out.unbind(0)], 0)
         return self._ffbs_with_callables(states, start)
 
@@ -1087,10 +1106,11 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         model and parameters stay untouched.
 
         ``route="auto"``: a built-in model of up to three state / observation components on a GPU takes one launch of
-        ``pf_path_score`` (float64 outputs) and a vector-Jacobian product through the builder and ``pack_params``; anything else -
-        user callables, ``LinearModel``, larger shapes, CPU tensors - torch autograd of the whole expression, which
-        ``route="torch"`` forces.  ``route="kernel"`` raises where the kernel does not apply.  An observation that is NaN in all
-        its elements contributes no observation term (``filters/particle/score.py``)."""
+        ``pf_path_score``, a ``LinearModel`` of up to eight under a linear-Gaussian observation one of ``pf_path_score_linear``
+        (float64 outputs both), then a vector-Jacobian product through the builder and ``pack_params``; anything else - user
+        callables, larger shapes, CPU tensors - torch autograd of the whole expression, which ``route="torch"`` forces.
+        ``route="kernel"`` raises where no kernel applies.  An observation that is NaN in all its elements contributes no
+        observation term (``filters/particle/score.py``)."""
         from .score import path_score
 
         assert self._model is not None, "Model has not been initialized!"

@@ -69,6 +69,15 @@ def kind_has_kernel(k, x: torch.Tensor) -> bool:
     return not k.is_user and k.hid_kind != L.HID_LINEAR_MAT and k.dim <= L.MAX_D and k.obs_dim is not None and k.obs_dim <= L.MAX_O
 
 
+def linear_kind_has_kernel(k, x: torch.Tensor) -> bool:
+    """``PF_HID_LINEAR_MAT`` (``LinearModel``) under a linear-Gaussian observation with ``D, O <= 8``, tensors on a GPU
+    (``pf_path_score_linear``, ``pf_smooth_ffbs_linear``)."""
+    if k is None or not x.is_cuda:
+        return False
+    return (not k.is_user and k.hid_kind == L.HID_LINEAR_MAT and k.obs_kind == L.OBS_LINEAR and 1 <= k.dim <= L.LIN_MAX_D
+            and k.obs_dim is not None and 1 <= k.obs_dim <= L.LIN_MAX_O)
+
+
 def kernel_applies(ctx, x: torch.Tensor) -> bool:
     return ctx is not None and kind_has_kernel(ctx.kind, x)
 

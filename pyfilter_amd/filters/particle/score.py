@@ -9,8 +9,11 @@ its gradient-based PMMH proposal (``_model_likelihood``, ``inference/batch/mcmc/
   streaming launch gives the transition / observation sums and their gradient with respect to the kernels' parameter rows; the
   step from rows to the caller's parameters is a vector-Jacobian product through the model builder and ``pack_params`` (torch
   autograd over ``(B, NP)`` tensors), the initial term one ``(N, B)`` evaluation;
-* anything else (user callables, ``LinearModel``, larger shapes, CPU tensors) or ``route="torch"``: torch autograd of the whole
-  expression, the reference's arithmetic.
+* a ``LinearModel`` of up to eight components under a linear-Gaussian observation of up to eight, on a GPU:
+  ``pf_path_score_linear`` (``csrc/pf_linear_smooth.hpp``) - the same scheme in that kind's row layout
+  ``[A | b | s | A_o | b_o | s_o]``; the vector-Jacobian product goes through ``linear_rows`` (``pack_params``' branch of the kind);
+* anything else (user callables, larger shapes, CPU tensors) or ``route="torch"``: torch autograd of the whole expression, the
+  reference's arithmetic.
 
 Two deviations from the reference's expression, on both routes: an observation that is NaN in all its elements
 contributes no observation term, as the filters skip it (the reference's sum would be NaN); and the kernel route's outputs are
@@ -25,13 +28,14 @@ from ... import _lib as L
 from ... import ops
 from ...timeseries import AffineProcess, TimeseriesState
 from ...timeseries.models import pack_params
-from .forecast import kind_has_kernel, tape_soa
+from .forecast import kind_has_kernel, linear_kind_has_kernel, tape_soa
 
 ROUTES = ("auto", "kernel", "torch")
 
 
 def kernel_applies(model, paths: torch.Tensor) -> bool:
-    return kind_has_kernel(getattr(model, "kernel_kind", None), paths)
+    kind = getattr(model, "kernel_kind", None)
+    return kind_has_kernel(kind, paths) or linear_kind_has_kernel(kind, paths)
 
 
 def _normal_base(dist):
@@ -116,7 +120,8 @@ def path_score(filter_, paths: torch.Tensor, y: torch.Tensor, theta: Optional[Ma
     has_event = model.hidden.n_dim > 0
     on_kernel = route != "torch" and kernel_applies(model, paths)
     if route == "kernel" and not on_kernel:
-        raise L.PfAmdError("path_score: no kernel for this model / device (built-in kinds with D, O <= 3 on a GPU)")
+        raise L.PfAmdError("path_score: no kernel for this model / device (built-in kinds with D, O <= 3 and LinearModel with "
+                           "D, O <= 8 under a linear-Gaussian observation, on a GPU)")
 
     if not on_kernel:
         with torch.enable_grad() if leaves is not None else torch.no_grad():
@@ -140,7 +145,8 @@ def path_score(filter_, paths: torch.Tensor, y: torch.Tensor, theta: Optional[Ma
     with torch.enable_grad() if leaves is not None else torch.no_grad():
         rows = pack_params(model, b, dtype, device)
         init = initial_term(model.hidden, paths[0])
-    sums, grad_rows = ops.path_score(kind, rows.detach().contiguous(), soa, y)
+    run = ops.path_score_linear if kind.hid_kind == L.HID_LINEAR_MAT else ops.path_score
+    sums, grad_rows = run(kind, rows.detach().contiguous(), soa, y)
     value = sums + init.detach().to(torch.float64).reshape(-1)
     value = value if batched else value[0]
     if leaves is None:

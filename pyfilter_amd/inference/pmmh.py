@@ -96,15 +96,23 @@ class GradientBasedProposal(RandomWalk):
     the reverse kernel at their own centres, so the chain targets the posterior whatever the drift.  A chain whose gradient is
     not finite (a filter that lost all its weight) gets no drift: the random walk's kernel.
 
+    ``route`` is handed to ``ParticleFilter.smooth`` (see there).  With ``"kernel"`` the backward simulation of a ``LinearModel``
+    runs on ``pf_smooth_ffbs_linear`` with Philox draws keyed by the filter's seed; together with ``pf_path_score_linear``, which
+    ``path_score`` takes by itself, a move on a matrix model is kernels end to end - and needs O(N S) memory, not the logits route's
+    ``(N, N, B, D)`` tensor per step.  ``"auto"`` keeps that model's torch-generator draws.
+
     The filter must record all its states (``record_states=True``), as the reference asserts.  ``exchange`` is ``RandomWalk``'s:
     after an accepted move the chain takes over the kernel built at the accepted value."""
 
-    def __init__(self, scale=1e-2, method: str = "ffbs", use_second_order: bool = False):
+    def __init__(self, scale=1e-2, method: str = "ffbs", use_second_order: bool = False, route: str = "auto"):
         if use_second_order:
             raise NotImplementedError("Currently does not support `use_second_order`!")
+        if route not in ("auto", "kernel", "torch"):
+            raise ValueError(f"GradientBasedProposal: route must be one of ('auto', 'kernel', 'torch'), got {route!r}")
         super().__init__(scale)
         self._eps = scale ** 2.0 / 2.0
         self._method = method
+        self._route = route
 
     def build(self, theta, state, filter_, y):
         states = state.filter_state.states
@@ -115,7 +123,7 @@ class GradientBasedProposal(RandomWalk):
         if isinstance(filter_, ParticleFilter):
             gen = torch.Generator(device=states[-1].timeseries_state.value.device)
             gen.manual_seed((filter_._seed * 0x9E3779B1 + filter_._draws) & 0x7FFFFFFFFFFFFFFF)
-            paths = filter_.smooth(states, self._method, generator=gen)
+            paths = filter_.smooth(states, self._method, generator=gen, route=self._route)
         else:
             paths = filter_.smooth(states, self._method)
         names = theta.names()

@@ -425,6 +425,33 @@ def path_score(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: torch.Ten
     return value, grad
 
 
+def path_score_linear(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``path_score`` for the ``PF_HID_LINEAR_MAT`` kind (``LinearModel`` under a linear-Gaussian observation, ``D, O <= 8``;
+    pf_path_score_linear): ``(value (B,), grad_rows (B, NP))``, both float64, the gradient in that kind's row layout
+    ``[A D*D | b D | s D | A_o O*D | b_o O | s_o O]``.  Same conventions for ``y`` and its NaN rows."""
+    L.require_gpu(paths_soa, y, params)
+    s, d, b, n = paths_soa.shape
+    o = int(kind.obs_dim)
+    dt, dev = paths_soa.dtype, paths_soa.device
+    assert paths_soa.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
+    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+        raise L.PfAmdError(f"path_score_linear: paths {tuple(paths_soa.shape)} / rows {tuple(params.shape)} do not match the model kind")
+    yy = y.to(device=dev, dtype=dt).reshape(s - 1, -1, o).contiguous() if s >= 2 else torch.zeros((1, 1, o), dtype=dt, device=dev)
+    rows = yy.shape[1]
+    if rows not in (1, b):
+        raise L.PfAmdError(f"observations of shape {tuple(y.shape)} do not broadcast against batch {b}")
+    value = torch.empty(b, dtype=torch.float64, device=dev)
+    grad = torch.empty((b, params.shape[1]), dtype=torch.float64, device=dev)
+    nbytes = C.c_size_t(0)
+    if s >= 2 and 1 <= d <= L.LIN_MAX_D and 1 <= o <= L.LIN_MAX_O:  # (otherwise pf_path_score_linear itself refuses the call)
+        L.check(L.load().pf_path_score_linear_workspace_bytes(n, b, s, d, o, C.byref(nbytes)), "pf_path_score_linear_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=dev)
+    mod = make_model_struct(kind, params)
+    L.check(L.load().pf_path_score_linear(C.byref(mod), paths_soa.data_ptr(), yy.data_ptr(), rows, value.data_ptr(), grad.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), s, n, b, L.dtype_code(dt), L.stream_ptr()), "pf_path_score_linear")
+    return value, grad
+
+
 def initial_sample_soa(m0, s0, n: int, b: int, d: int, dtype, device, seed: int, z: Optional[torch.Tensor] = None):
     x = torch.empty((d, b, n), dtype=dtype, device=device)
     L.require_gpu(x, z)
@@ -469,17 +496,23 @@ def debug_draw_normals(seed: int, steps: int, n: int, b: int, d: int, dtype, dev
 
 
 TRACE_LEN = 2048  # launch records the library keeps per thread (PF_TRACE_LEN)
+# the entry point a record's SPEC names (csrc/pf_linear_smooth.hpp: PF_TRACE_*); every other SPEC is a launch of pf_filter_run
+TRACE_ENTRY = {20: "pf_smooth_ffbs_linear", 21: "pf_path_score_linear"}
 
 
 def debug_launch_trace(last: int = 64):
     """The step-kernel instantiations of this thread's latest fused launches, oldest first, as dicts (pf_debug_launch_trace_fields;
-    ``LEAF``: the launch took the one-column leaf of the step kernel)."""
+    ``LEAF``: the launch took the one-column leaf of the step kernel).  ``pf_smooth_ffbs_linear`` and ``pf_path_score_linear``
+    leave one record per call too; ``ENTRY`` names the entry point a record belongs to (``TRACE_ENTRY``, else ``pf_filter_run``)."""
     buf = (C.c_int32 * (len(TRACE_FIELDS) * last))()
     n = L.load().pf_debug_launch_trace_fields(buf, last, len(TRACE_FIELDS))
     if n < 0:
         L.check(n, "pf_debug_launch_trace_fields")
     k = len(TRACE_FIELDS)
-    return [dict(zip(TRACE_FIELDS, buf[i * k:(i + 1) * k])) for i in range(n)]
+    recs = [dict(zip(TRACE_FIELDS, buf[i * k:(i + 1) * k])) for i in range(n)]
+    for r in recs:
+        r["ENTRY"] = TRACE_ENTRY.get(r["SPEC"], "pf_filter_run")
+    return recs
 
 
 def debug_leaf_residency(proposal: int, mk: int):
@@ -779,4 +812,27 @@ def smooth_ffbs(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hist: tor
     L.check(L.load().pf_smooth_ffbs(C.byref(m), x_hist.data_ptr(), logw_hist.data_ptr(), x_last.data_ptr(), L.ptr(u),
                                     seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), s, n, b, L.dtype_code(x_hist.dtype),
                                     L.stream_ptr()), "pf_smooth_ffbs")
+    return out
+
+
+def smooth_ffbs_linear(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hist: torch.Tensor, x_last: torch.Tensor,
+                       u: Optional[torch.Tensor], seed: int) -> torch.Tensor:
+    """``smooth_ffbs`` for the ``PF_HID_LINEAR_MAT`` kind (``LinearModel``, ``D <= 8``; pf_smooth_ffbs_linear): the same
+    layouts, tape and Philox keys, O(N S) memory where the torch-logits route holds an ``(N, N, B, D)`` tensor per step."""
+    L.require_gpu(x_hist, logw_hist, x_last, u, params)
+    s, d, b, n = x_hist.shape
+    assert logw_hist.shape == (s, b, n) and x_last.shape == (d, b, n)
+    assert x_hist.is_contiguous() and logw_hist.is_contiguous() and x_last.is_contiguous()
+    assert params.is_contiguous() and params.dtype == x_hist.dtype and params.shape[0] == b
+    o = int(kind.obs_dim)
+    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads by the kind)
+        raise L.PfAmdError(f"smooth_ffbs_linear: history {tuple(x_hist.shape)} / rows {tuple(params.shape)} do not match the model kind")
+    if u is not None:
+        u = u.to(x_hist.dtype).contiguous()
+        assert u.shape == (s - 1, b, n)
+    out = torch.empty_like(x_hist)
+    m = make_model_struct(kind, params)
+    L.check(L.load().pf_smooth_ffbs_linear(C.byref(m), x_hist.data_ptr(), logw_hist.data_ptr(), x_last.data_ptr(), L.ptr(u),
+                                           seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), s, n, b, L.dtype_code(x_hist.dtype),
+                                           L.stream_ptr()), "pf_smooth_ffbs_linear")
     return out
