@@ -239,6 +239,22 @@ int pf_path_score_linear_workspace_bytes(int64_t N, int64_t B, int64_t S, int64_
 int pf_path_score_linear(const pf_model* model, const void* paths, const void* y, int64_t y_rows, double* value, double* grad,
                          void* ws, size_t ws_bytes, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
 
+/* pf_forecast for PF_HID_LINEAR_MAT under PF_OBS_LINEAR, 1 <= D, O <= 8 (what particle/state.py:173-174 `predict_path` is for,
+ * for stochproc's LinearModel): the same inputs, draws (streams, addressing: e is number (b N + i) 8 + o), moments, conventions
+ * and layouts, in one launch for the whole horizon plus one that adds the tiles' sums.  What differs: the parameter row is that
+ * kind's [ A | b | s | A_obs | b_obs | s_obs ], and predictive COVARIANCES are optional outputs - x_cov (steps,B,D,D) and
+ * y_cov (steps,B,O,O), both or neither (NULL: not computed) - cov_ij = sum W (x_i - mean_i)(x_j - mean_j) from sums centred about
+ * a pivot (both triangles written from one sum, the diagonal of x_cov IS x_var), y_cov Rao-Blackwellised like y_var: the
+ * covariance of the conditional means b_obs + A_obs x plus sum W diag(s_obs^2).
+ * Any other kind, PF_OBS_SV and D or O outside 1 .. 8 are PF_EUNSUPPORTED; steps < 1, N or B < 1, a null mandatory pointer and
+ * exactly one of x_cov / y_cov are PF_EINVAL; a short workspace is PF_EWORKSPACE - all before any launch.
+ * ws: pf_forecast_linear_workspace_bytes(N, B, steps, D, O, covariance) bytes: 8 (1 + 2 D + 2 O [+ D (D - 1) / 2]) B per step,
+ * filter and tile of 1024 (D <= 4) or 512 particles. */
+int pf_forecast_linear_workspace_bytes(int64_t N, int64_t B, int steps, int64_t D, int64_t O, int covariance, size_t* bytes);
+int pf_forecast_linear(const pf_model* model, int steps, const void* x, const void* W, const void* z, const void* e, uint64_t seed,
+                       void* x_mean, void* x_var, void* y_mean, void* y_var, void* x_cov, void* y_cov, void* x_path, void* y_path,
+                       void* ws, size_t ws_bytes, int64_t N, int64_t B, int dtype, void* stream);
+
 /* hidden.initial_sample: x (D,B,N) <- m0[d] + s0[d] * z, z from `z` or Philox(seed). m0, s0: (D) host doubles.  Any D >= 1
  * (Philox: planes 3k .. 3k+2 draw at counter step k, so a state of D <= 3 draws what it always drew). */
 int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,

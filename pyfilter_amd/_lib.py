@@ -37,6 +37,7 @@ EXPORTS = (
     "pf_host_free", "pf_filter_observe", "pf_jitter_fit", "pf_jitter_apply", "pf_nested_sample_and_weight",
     "pf_forecast", "pf_forecast_workspace_bytes", "pf_path_score", "pf_path_score_workspace_bytes",
     "pf_path_score_linear", "pf_path_score_linear_workspace_bytes", "pf_smooth_ffbs_linear",
+    "pf_forecast_linear", "pf_forecast_linear_workspace_bytes",
 )
 
 
@@ -135,6 +136,9 @@ def load() -> C.CDLL:
     lib.pf_forecast.argtypes = [C.POINTER(PfModel), i32, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64, i32, vp]
     lib.pf_path_score_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
     lib.pf_path_score.argtypes = [C.POINTER(PfModel), vp, vp, i64, vp, vp, vp, sz, i64, i64, i64, i32, vp]
+    lib.pf_forecast_linear_workspace_bytes.argtypes = [i64, i64, i32, i64, i64, i32, C.POINTER(sz)]
+    lib.pf_forecast_linear.argtypes = [C.POINTER(PfModel), i32, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, i64,
+                                       i32, vp]
     lib.pf_path_score_linear_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, C.POINTER(sz)]
     lib.pf_path_score_linear.argtypes = [C.POINTER(PfModel), vp, vp, i64, vp, vp, vp, sz, i64, i64, i64, i32, vp]
     lib.pf_initial_sample.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u64, vp, i64, i64, i64, i32, vp]

@@ -1742,6 +1742,48 @@ extern "C" int pf_path_score_linear(const pf_model* model, const void* paths, co
     });
 }
 
+// ---- forecasting for PF_HID_LINEAR_MAT (pf_forecast_linear.hpp) -----------------------------------------------------------------
+#include "pf_forecast_linear.hpp"
+static inline int64_t linfc_tiles(int64_t N, int D) { return (N + PF_BLOCK * linfc_items(D) - 1) / (PF_BLOCK * linfc_items(D)); }
+extern "C" int pf_forecast_linear_workspace_bytes(int64_t N, int64_t B, int steps, int64_t D, int64_t O, int covariance, size_t* bytes) {
+    if (!bytes || bad_shape(N, B) || steps < 1) return PF_EINVAL;
+    if (D < 1 || D > PF_LIN_MAXD || O < 1 || O > PF_LIN_MAXO) return PF_EUNSUPPORTED;
+    *bytes = sizeof(double) * (size_t)steps * (size_t)linfc_q((int)D, (int)O, covariance != 0) * (size_t)B * (size_t)linfc_tiles(N, (int)D);
+    return PF_OK;
+}
+extern "C" int pf_forecast_linear(const pf_model* model, int steps, const void* x, const void* W, const void* z, const void* e,
+                                  uint64_t seed, void* x_mean, void* x_var, void* y_mean, void* y_var, void* x_cov, void* y_cov,
+                                  void* x_path, void* y_path, void* ws, size_t ws_bytes, int64_t N, int64_t B, int dtype, void* stream) {
+    if (!model || !model->params || steps < 1 || !x || !x_mean || !x_var || !y_mean || !y_var || !ws || (!x_cov) != (!y_cov)) return PF_EINVAL;
+    int rc = check_linmat(model);
+    if (rc) return rc;
+    if (bad_shape(N, B)) return PF_EINVAL;
+    const int D = model->dim, O = model->obs_dim;
+    const bool cov = x_cov != nullptr;
+    size_t need = 0;
+    rc = pf_forecast_linear_workspace_bytes(N, B, steps, D, O, cov, &need);
+    if (rc) return rc;
+    if (ws_bytes < need) return PF_EWORKSPACE;
+    const int tiles = (int)linfc_tiles(N, D);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return with_d8(D, [&](auto d) {
+            return with_bool(cov, [&](auto c) {
+                constexpr int DD = decltype(d)::value;
+                constexpr bool CV = decltype(c)::value;
+                hipLaunchKernelGGL((k_forecast_linmat_part<T, DD, CV>), dim3(tiles, (int)B), dim3(PF_BLOCK), 0, st, (const T*)model->params, O,
+                                   steps, (const T*)x, (const T*)W, (const T*)z, (const T*)e, seed, (double*)ws, (T*)x_path, (T*)y_path, N,
+                                   (int)B);
+                hipLaunchKernelGGL((k_forecast_linmat_final<T, DD, CV>), dim3(steps, (int)B), dim3(PF_BLOCK), 0, st, (const T*)model->params, O,
+                                   (const T*)x, (const double*)ws, (T*)x_mean, (T*)x_var, (T*)y_mean, (T*)y_var, (T*)x_cov, (T*)y_cov, N,
+                                   (int)B, tiles);
+                return launch_status();
+            });
+        });
+    });
+}
+
 extern "C" int pf_initial_sample(const double* m0, const double* s0, const void* z, uint64_t seed, void* x, int64_t N,
                                  int64_t B, int64_t D, int dtype, void* stream) {
     if (!m0 || !s0 || !x || bad_shape(N, B) || D < 1) return PF_EINVAL;

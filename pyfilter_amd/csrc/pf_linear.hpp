@@ -68,8 +68,10 @@ __device__ inline void lin_chol_inplace(double* m, int n, int ld) {
 
 // Forms the per-filter constants of column b into `lc` (every thread of the workgroup calls it; ends with a barrier).
 // `lgo`: the optimal proposal's algebra is needed (sample_and_weight) / `pre`: the innovation covariance is needed (pre_weight).
+// Always inlined: left to the inliner's budget, the forecast kernels' further call sites turned the one in
+// k_linmat_sample_and_weight into a call (100 -> 168 VGPRs at float D = 8; profiles/forecast_linear_kernel_resources.txt).
 template <typename T, int D>
-__device__ inline void lin_prepare(LinConsts<T>& lc, LinWork& w, const T* __restrict__ row, int O, const T* __restrict__ yrow,
+__device__ __forceinline__ void lin_prepare(LinConsts<T>& lc, LinWork& w, const T* __restrict__ row, int O, const T* __restrict__ yrow,
                                    bool lgo, bool pre) {
     const int tid = threadIdx.x;
     const int NP = D * D + 2 * D + O * D + 2 * O;

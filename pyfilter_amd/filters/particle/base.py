@@ -22,7 +22,8 @@ from ...timeseries.models import pack_params
 from ..base import BaseFilter
 from ..result import FilterResult
 from ..schedule import expand
-from .forecast import Forecast, kernel_applies, kernel_forecast, normalized_weights, torch_forecast
+from .forecast import (Forecast, kernel_applies, kernel_forecast, linear_kernel_forecast, linear_kind_has_kernel, normalized_weights,
+                       torch_forecast)
 from .proposals import Bootstrap, LinearGaussianObservations, Proposal
 from .proposals.base import KernelContext
 from .state import ParticleFilterCorrection, ParticleFilterPrediction
@@ -234,7 +235,7 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         return prediction.create_state_from_prediction(self._model, propagate=self._proposal._propagate)
 
     def forecast(self, state, steps: int, paths: bool = False, z: Optional[torch.Tensor] = None, e: Optional[torch.Tensor] = None,
-                 seed: Optional[int] = None) -> Forecast:
+                 seed: Optional[int] = None, route: str = "auto", covariance: bool = False) -> Forecast:
         """The predictive law ``steps`` moves of the hidden process ahead of ``state`` - a ``ParticleFilterCorrection`` or a
         ``FilterResult`` (then its latest state): weighted predictive mean and variance of the state and of the observation at
         every move, and with ``paths`` the particles' trajectories in ``predict_path``'s layout (``filters/particle/forecast.py``).
@@ -245,22 +246,37 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         a forecast counter of its own.  Nothing of the filter's run changes: its draw counter, the state and its weights stay as
         they are, so a run continued after a forecast is the run without one.
 
-        A built-in model of up to three state / observation components on a GPU takes one launch of ``pf_forecast``; anything
-        else the same computation as torch operations."""
+        ``route="auto"``: a built-in model of up to three state / observation components on a GPU takes one launch of
+        ``pf_forecast``; anything else the same computation as torch operations, which ``route="torch"`` forces.
+        ``route="kernel"`` additionally sends a ``LinearModel`` (a ``RandomWalk`` of four to eight dimensions included) of up to
+        eight state / observation components under a linear-Gaussian observation to one launch of ``pf_forecast_linear``, and
+        raises where no kernel applies.
+
+        ``covariance``: the forecast also carries ``x_covariance (steps, [B], D, D)`` and ``y_covariance (steps, [B], O, O)`` -
+        from ``pf_forecast_linear`` or from torch operations; ``pf_forecast`` has none (``"auto"``: the torch route)."""
+        if route not in ("auto", "kernel", "torch"):
+            raise ValueError(f"forecast: route must be one of ('auto', 'kernel', 'torch'), got {route!r}")
         if isinstance(state, FilterResult):
             state = state.latest_state
         steps = int(steps)
         if steps < 1:
             raise L.PfAmdError("forecast: steps must be at least 1")
+        x = state.timeseries_state
+        ctx = self._ensure_context()
+        builtin = route != "torch" and not covariance and kernel_applies(ctx, x.value)
+        linear = route == "kernel" and ctx is not None and linear_kind_has_kernel(ctx.kind, x.value)
+        if route == "kernel" and not (builtin or linear):
+            raise L.PfAmdError("forecast: no kernel for this model / device (built-in kinds with D, O <= 3 - without covariances - and "
+                               "LinearModel with D, O <= 8 under a linear-Gaussian observation, on a GPU)")
         if seed is None:
             self._forecasts += 1
             seed = (self._seed ^ (_GOLD * (self._forecasts + 0xF0CA57))) & _M64
-        x = state.timeseries_state
         w = normalized_weights(state.weights)
-        ctx = self._ensure_context()
-        if kernel_applies(ctx, x.value):
+        if builtin:
             return kernel_forecast(ctx, self._model.n_dim > 0, x, w, steps, paths, z, e, seed)
-        return torch_forecast(self._model, x, w, steps, paths, z, e, seed)
+        if linear:
+            return linear_kernel_forecast(ctx, self._model.n_dim > 0, x, w, steps, paths, z, e, seed, covariance)
+        return torch_forecast(self._model, x, w, steps, paths, z, e, seed, covariance)
 
     def _copy_seed(self) -> int:
         """A copy draws its own random numbers (the reference's copies share torch's global generator, i.e. never repeat

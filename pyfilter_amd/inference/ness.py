@@ -328,10 +328,10 @@ class BaseOnlineAlgorithm:
         """Weighted mean of the stacked (constrained) parameters over the theta-particles."""
         return theta_normalize(state.w) @ self.theta.stack_parameters(True)
 
-    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None):
+    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None, route: str = "auto", covariance: bool = False):
         """The posterior predictive ``steps`` moves ahead: the filters' forecasts mixed with the normalised theta-weights
         (``smc2.posterior_forecast``)."""
-        return posterior_forecast(self.filter, state, steps, seed)
+        return posterior_forecast(self.filter, state, steps, seed, None, route, covariance)
 
 
 class NESS(BaseOnlineAlgorithm):

@@ -656,17 +656,20 @@ class SMC2:
             vals, w = self.shard.all_gather(vals), self.shard.all_gather(w)
         return theta_normalize(w) @ vals
 
-    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None) -> Forecast:
-        """The posterior predictive ``steps`` moves ahead: the filters' forecasts (``ParticleFilter.forecast``) mixed with the
-        normalised theta-weights over ALL theta-particles (``mix_forecasts``)."""
-        return posterior_forecast(self.filter, state, steps, seed, self.shard)
+    def forecast(self, state: SMC2State, steps: int, seed: Optional[int] = None, route: str = "auto", covariance: bool = False) -> Forecast:
+        """The posterior predictive ``steps`` moves ahead: the filters' forecasts (``ParticleFilter.forecast``, which takes
+        ``route`` and ``covariance``) mixed with the normalised theta-weights over ALL theta-particles (``mix_forecasts``)."""
+        return posterior_forecast(self.filter, state, steps, seed, self.shard, route, covariance)
 
 
-def posterior_forecast(filter_, state: SMC2State, steps: int, seed: Optional[int] = None, shard: Optional[Shard] = None) -> Forecast:
+def posterior_forecast(filter_, state: SMC2State, steps: int, seed: Optional[int] = None, shard: Optional[Shard] = None,
+                       route: str = "auto", covariance: bool = False) -> Forecast:
     """``mix_forecasts`` of the forecasts of a state's filters under its theta-weights; on a collective shard the filters' moments
-    and the weights are all-gathered first, as ``posterior_mean`` gathers the parameters."""
-    fc, w = filter_.forecast(state.filter_state, steps, seed=seed), state.w
+    (covariances included) and the weights are all-gathered first, as ``posterior_mean`` gathers the parameters."""
+    fc, w = filter_.forecast(state.filter_state, steps, seed=seed, route=route, covariance=covariance), state.w
     if shard is not None and shard.collective:
-        fc = Forecast(*(shard.all_gather(m, dim=1) for m in (fc.x_mean, fc.x_variance, fc.y_mean, fc.y_variance)))
+        gathered = [shard.all_gather(m, dim=1) for m in (fc.x_mean, fc.x_variance, fc.y_mean, fc.y_variance)]
+        covs = [None if c is None else shard.all_gather(c, dim=1) for c in (fc.x_covariance, fc.y_covariance)]
+        fc = Forecast(*gathered, None, *covs)
         w = shard.all_gather(w)
     return mix_forecasts(theta_normalize(w), fc)

@@ -397,6 +397,44 @@ def forecast_soa(kind, params, steps: int, x: torch.Tensor, W: Optional[torch.Te
     return (*moments, x_path, y_path)
 
 
+def forecast_linear_soa(kind, params, steps: int, x: torch.Tensor, W: Optional[torch.Tensor], z: Optional[torch.Tensor] = None,
+                        e: Optional[torch.Tensor] = None, seed: int = 0, paths: bool = False, covariance: bool = False):
+    """``forecast_soa`` for the ``PF_HID_LINEAR_MAT`` kind (``LinearModel`` under a linear-Gaussian observation, ``D, O <= 8``;
+    pf_forecast_linear), the same inputs and layouts: ``(x_mean, x_var (steps, B, D), y_mean, y_var (steps, B, O), x_cov (steps, B,
+    D, D) | None, y_cov (steps, B, O, O) | None, x_path (steps, D, B, N) | None, y_path (steps, O, B, N) | None)``."""
+    L.require_gpu(x, W, z, e, params)
+    d, b, n = x.shape
+    o, steps = int(kind.obs_dim), int(steps)
+    dt, dev = x.dtype, x.device
+    assert x.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
+    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+        raise L.PfAmdError(f"forecast_linear_soa: state {tuple(x.shape)} / rows {tuple(params.shape)} do not match the model kind")
+    if W is not None:
+        assert tuple(W.shape) == (b, n) and W.is_contiguous() and W.dtype == dt
+    if z is not None:
+        assert tuple(z.shape) == (steps, d, b, n) and z.is_contiguous() and z.dtype == dt
+    if e is not None:
+        assert tuple(e.shape) == (steps, o, b, n) and e.is_contiguous() and e.dtype == dt
+    rows = max(steps, 0)
+    moments = [torch.empty((rows, b, k), dtype=dt, device=dev) for k in (d, d, o, o)]
+    covs = [torch.empty((rows, b, k, k), dtype=dt, device=dev) if covariance else None for k in (d, o)]
+    x_path = torch.empty((rows, d, b, n), dtype=dt, device=dev) if paths else None
+    y_path = torch.empty((rows, o, b, n), dtype=dt, device=dev) if paths else None
+    nbytes = C.c_size_t(0)
+    if steps >= 1 and 1 <= d <= L.LIN_MAX_D and 1 <= o <= L.LIN_MAX_O:  # (otherwise pf_forecast_linear itself refuses the call)
+        L.check(L.load().pf_forecast_linear_workspace_bytes(n, b, steps, d, o, int(bool(covariance)), C.byref(nbytes)),
+                "pf_forecast_linear_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=dev)
+    mod = make_model_struct(kind, params)
+    L.check(
+        L.load().pf_forecast_linear(C.byref(mod), steps, L.ptr(x), L.ptr(W), L.ptr(z), L.ptr(e), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    *[m.data_ptr() for m in moments], L.ptr(covs[0]), L.ptr(covs[1]), L.ptr(x_path), L.ptr(y_path),
+                                    ws.data_ptr(), ws.numel(), n, b, L.dtype_code(dt), L.stream_ptr()),
+        "pf_forecast_linear",
+    )
+    return (*moments, *covs, x_path, y_path)
+
+
 def path_score(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The complete-data log-likelihood of the trajectories ``paths_soa (S, D, B, N)`` (``smooth_ffbs``' layout) under a built-in
     model and its gradient with respect to the parameter rows ``params (B, NP)``, in one streaming launch (pf_path_score):
