@@ -572,6 +572,23 @@ int pf_smooth_ffbs(const pf_model* model, const void* x_hist, const void* logw_h
 int pf_smooth_ffbs_linear(const pf_model* model, const void* x_hist, const void* logw_hist, const void* x_last, const void* u,
                           uint64_t seed, void* out, int64_t S, int64_t N, int64_t B, int dtype, void* stream);
 
+/* method "ffbs-mh" (no counterpart in the reference): backward simulation by Metropolis-Hastings (Bunch & Godsill 2013) - O(N K)
+ * per step where "ffbs" is O(N^2); K = mcmc_steps = 0 is "fl", K -> inf is "ffbs".  idx_last (B, N): the resampled indices of the
+ * last state (done by the caller, as for pf_smooth_ffbs).  k_{S-1} = idx_last[b][j], out[S-1][j] = x[S-1][k_{S-1}]; for
+ * t = S-2 .. 0 trajectory j starts at i = anc[t+1][b][k_{t+1}] with l = l_t(i) - or -inf where the sanitised logw[t][i] is
+ * -inf - and makes K independence-sampler moves: the proposal i' is the first candidate with cdf_t[i'] > u1 cdf_t[N-1] (none: the
+ * last one of positive mass), cdf_t the float64 inclusive running sum of exp(sanitised logw[t] - max); it is accepted iff
+ * l = -inf or log(u2) < l_t(i') - l; then k_t = i, out[t][j] = x[t][k_t], idx_out[t][b][j] = k_t (idx_out (S, B, N), may be NULL).
+ * l_t(i) = log p(out[t+1][j] | x[t][i]) up to a constant of the filter.  u (S-1, K, 2, B, N): [t][r][0] proposes, [t][r][1]
+ * accepts; NULL -> Philox: call (b N + j) K + r of (seed, stream 10, step t), u1 and u2 its first two numbers.
+ * Built-in kinds with D <= 3 and PF_HID_LINEAR_MAT (D, O in 1 .. 8, PF_OBS_LINEAR); anything else: PF_EUNSUPPORTED.  K < 0, S < 1,
+ * N or B < 1, a null pointer (u, idx_out and - for S = 1 - ws excepted), ws_bytes below pf_smooth_mh_workspace_bytes: PF_EINVAL -
+ * before any launch: the outputs are untouched.  S = 1 writes out[0] and idx_out[0] and nothing else. */
+int pf_smooth_mh_workspace_bytes(int64_t N, int64_t B, int64_t S, size_t* bytes);
+int pf_smooth_mh(const pf_model* model, const void* x_hist, const void* logw_hist, const int32_t* anc_hist,
+                 const int32_t* idx_last, const void* u, uint64_t seed, int mcmc_steps, void* out, int32_t* idx_out,
+                 int64_t S, int64_t N, int64_t B, int dtype, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------ *
  * test support (no reference counterpart): lets a parity test feed the oracle the very draws a *production* run used
  * ------------------------------------------------------------------------------------------------------------ */
@@ -583,7 +600,8 @@ int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_steps, void* 
 
 /* The step-kernel instantiations the calling thread's most recent pf_filter_run launches selected, oldest first:
  * out[i] = { step, sizeof(T), D, VEC, MODE, PROP, FAST, SPEC, MK, MULTI } (10 int32 per record, the last 2048 are kept).
- * pf_smooth_ffbs_linear and pf_path_score_linear leave a record of their own per call: SPEC = 20 and 21, step 0, sizeof(T), D.
+ * pf_smooth_ffbs_linear, pf_path_score_linear and pf_smooth_mh leave a record of their own per call: SPEC = 20, 21 and 22, step 0,
+ * sizeof(T), D.
  * Returns the number of records written (>= 0) or a negative PF_E* code. */
 int pf_debug_launch_trace(int32_t* out, int max_records);
 /* The same with `fields` (1 .. 11) int32 per record: field 10 = the launch took the one-column leaf of the step kernel. */

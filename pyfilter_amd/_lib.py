@@ -38,6 +38,7 @@ EXPORTS = (
     "pf_forecast", "pf_forecast_workspace_bytes", "pf_path_score", "pf_path_score_workspace_bytes",
     "pf_path_score_linear", "pf_path_score_linear_workspace_bytes", "pf_smooth_ffbs_linear",
     "pf_forecast_linear", "pf_forecast_linear_workspace_bytes",
+    "pf_smooth_mh", "pf_smooth_mh_workspace_bytes",
 )
 
 
@@ -150,6 +151,8 @@ def load() -> C.CDLL:
     lib.pf_smooth_fixed_lag.argtypes = [vp, vp, vp, i64, i64, i64, i64, i32, vp]
     lib.pf_smooth_ffbs.argtypes = [C.POINTER(PfModel), vp, vp, vp, vp, u64, vp, i64, i64, i64, i32, vp]
     lib.pf_smooth_ffbs_linear.argtypes = [C.POINTER(PfModel), vp, vp, vp, vp, u64, vp, i64, i64, i64, i32, vp]
+    lib.pf_smooth_mh_workspace_bytes.argtypes = [i64, i64, i64, C.POINTER(sz)]
+    lib.pf_smooth_mh.argtypes = [C.POINTER(PfModel), vp, vp, vp, vp, vp, u64, i32, vp, vp, i64, i64, i64, i32, vp, sz, vp]
     lib.pf_observed_flags.argtypes = [vp, i64, i64, i32, vp, vp]
     lib.pf_theta_ess.argtypes = [vp, i64, i64, i32, vp, vp]
     lib.pf_theta_path.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, u64, vp, vp]

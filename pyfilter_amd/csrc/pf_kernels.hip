@@ -2081,6 +2081,49 @@ extern "C" int pf_smooth_ffbs_linear(const pf_model* model, const void* x_hist, 
     });
 }
 
+// ---- backward simulation by Metropolis-Hastings (pf_smooth_mh.hpp) ----------------------------------------------------------
+#include "pf_smooth_mh.hpp"
+// the cdf planes (S - 1, B, N) of doubles, then one int64 per (t, b)
+extern "C" int pf_smooth_mh_workspace_bytes(int64_t N, int64_t B, int64_t S, size_t* bytes) {
+    if (!bytes || bad_shape(N, B) || S < 1) return PF_EINVAL;
+    *bytes = sizeof(double) * (size_t)(S - 1) * (size_t)B * ((size_t)N + 1);
+    return PF_OK;
+}
+extern "C" int pf_smooth_mh(const pf_model* model, const void* x_hist, const void* logw_hist, const int32_t* anc_hist,
+                            const int32_t* idx_last, const void* u, uint64_t seed, int mcmc_steps, void* out, int32_t* idx_out,
+                            int64_t S, int64_t N, int64_t B, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    if (!model || !x_hist || !logw_hist || !anc_hist || !idx_last || !out || mcmc_steps < 0 || S < 1 || bad_shape(N, B)) return PF_EINVAL;
+    if (dtype != PF_F32 && dtype != PF_F64) return PF_EINVAL;
+    int rc = check_model(model);
+    if (rc) return rc;
+    size_t need = 0;
+    pf_smooth_mh_workspace_bytes(N, B, S, &need);
+    if (need > 0 && (!ws || ws_bytes < need)) return PF_EINVAL;
+    if ((S - 1) * B > INT32_MAX) return PF_EUNSUPPORTED;  // (the cdf kernel's grid)
+    const bool mat = model->hid_kind == PF_HID_LINEAR_MAT;
+    const ModelDesc md = to_desc(model);
+    const dim3 grid((unsigned)((N + PF_BLOCK - 1) / PF_BLOCK), (int)B);
+    double* cdf = (double*)ws;
+    int64_t* last_pos = (int64_t*)(cdf + (S - 1) * B * N);
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        trace_launch(0, (int)sizeof(T), model->dim, 1, 0, 0, 0, PF_TRACE_SMOOTH_MH, 0, 0);
+        if (S > 1) {
+            hipLaunchKernelGGL((k_smooth_mh_cdf<T>), dim3((unsigned)((S - 1) * B)), dim3(PF_BLOCK), 0, st, (const T*)logw_hist, cdf, last_pos, N);
+            PF_CHECK_LAUNCH();
+        }
+        auto launch = [&](auto d, auto m) {
+            hipLaunchKernelGGL((k_smooth_mh<T, decltype(d)::value, decltype(m)::value>), grid, dim3(PF_BLOCK), 0, st, md, (const T*)model->params,
+                               (const T*)x_hist, (const T*)logw_hist, anc_hist, idx_last, (const T*)u, seed, mcmc_steps, (const double*)cdf,
+                               (const int64_t*)last_pos, (T*)out, idx_out, S, N, (int)B);
+            return launch_status();
+        };
+        if (mat) return with_d8(model->dim, [&](auto d) { return launch(d, std::true_type{}); });
+        return with_d3(model->dim, [&](auto d) { return launch(d, std::false_type{}); });
+    });
+}
+
 // ---- test support ----------------------------------------------------------------------------------------------------
 extern "C" int pf_debug_draw_normals(uint64_t seed, uint32_t step0, int64_t n_steps, void* out, int64_t N, int64_t B,
                                      int64_t D, int dtype, void* stream) {

@@ -1042,10 +1042,12 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
 
     def set_smoothing_tape(self, u: Optional[torch.Tensor]):
         """Parity mode for ``smooth(..., "ffbs")``: the uniforms of the backward draws, ``(S - 1, N, [B])`` (row t serves
-        the draw of state t given state t + 1) - ``None`` restores Philox."""
+        the draw of state t given state t + 1) - ``None`` restores Philox.  For ``"ffbs-mh"``: ``(S - 1, K, 2, N, [B])`` with
+        ``K = mcmc_steps`` (``[t][r][0]`` proposes, ``[t][r][1]`` accepts in round r of state t)."""
         self._ffbs_u = u
 
-    def smooth(self, states, method: str = "ffbs", generator: Optional[torch.Generator] = None, route: str = "auto") -> torch.Tensor:
+    def smooth(self, states, method: str = "ffbs", generator: Optional[torch.Generator] = None, route: str = "auto",
+               mcmc_steps: int = 8) -> torch.Tensor:
         """Smoothed trajectories ``(S, N, [B], [D])`` from recorded states: ``"fl"`` - every particle of the last state
         traced back along its ancestors (:136-152); ``"ffbs"`` - forward filtering, backward simulation (:105-134).  Both are
         one kernel launch over the state history for built-in models on the GPU; ``"ffbs"`` with user callables evaluates
@@ -1063,13 +1065,23 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
           a linear-Gaussian observation) on a GPU, the latter through ``pf_smooth_ffbs_linear``: O(N S) memory where the
           logits route holds an ``(N, N, [B], D)`` tensor per step.  ``PfAmdError`` where there is none (user callables, CPU
           tensors).
-        * ``"torch"``: the logits route for any model."""
+        * ``"torch"``: the logits route for any model.
+
+        ``"ffbs-mh"`` (no counterpart in the reference) is backward simulation by Metropolis-Hastings (Bunch & Godsill 2013,
+        ``pf_smooth_mh``): the last state is resampled as for ``"ffbs"``; going back, every trajectory starts at the parent of
+        its particle - the ``"fl"`` choice - and makes ``mcmc_steps`` independence-sampler moves: a candidate drawn from the
+        filter weights, accepted with the ratio of transition densities.  O(N K) per step where ``"ffbs"`` is O(N^2);
+        ``mcmc_steps=0`` is ancestor tracing from the resampled particles, ``mcmc_steps -> inf`` is ``"ffbs"``.  Kernel only
+        (``route="auto"`` and ``"kernel"``; built-in kinds and ``LinearModel`` with ``D, O <= 8``, states on a GPU): anything else
+        raises ``PfAmdError`` - use ``"ffbs"`` there.  ``"ffbs"`` and ``"fl"`` ignore ``mcmc_steps``."""
         states = list(states)
         low = method.lower()
-        if low not in ("ffbs", "fl"):
+        if low not in ("ffbs", "fl", "ffbs-mh"):
             raise NotImplementedError(f"Currently do not support '{method}'!")
         if route not in ("auto", "kernel", "torch"):
             raise ValueError(f"smooth: route must be one of ('auto', 'kernel', 'torch'), got {route!r}")
+        if low == "ffbs-mh" and int(mcmc_steps) < 0:
+            raise ValueError(f"smooth: mcmc_steps must be >= 0, got {mcmc_steps}")
         x_last = states[-1].timeseries_state.value
         on_gpu = x_last.is_cuda
         if low == "fl":
@@ -1081,6 +1093,10 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
         ctx = self._ensure_context()
         has_kernel = route != "torch" and ctx is not None and on_gpu and not ctx.kind.is_user
         matrix = has_kernel and ctx.kind.hid_kind == L.HID_LINEAR_MAT
+        if low == "ffbs-mh" and not has_kernel:
+            raise L.PfAmdError('smooth: "ffbs-mh" runs on its kernel only (built-in kinds and LinearModel with D, O <= 8 under a '
+                               'linear-Gaussian observation, states on a GPU, route "auto" or "kernel"): use "ffbs" for this '
+                               "model / device / route")
         if route == "kernel" and not has_kernel:
             raise L.PfAmdError("smooth: no backward-simulation kernel for this model / device (built-in kinds and LinearModel "
                                "with D, O <= 8 under a linear-Gaussian observation, states on a GPU)")
@@ -1095,6 +1111,18 @@ class ParticleFilter(BaseFilter[ParticleFilterCorrection, ParticleFilterPredicti
             idx = self._resampler(w_last)
         from ..utils import batched_gather
 
+        if low == "ffbs-mh":
+            x_hist, w_hist, anc_hist = self._history(states)
+            s1, k, (b, n) = len(states) - 1, int(mcmc_steps), x_hist.shape[2:]
+            u = self._ffbs_u
+            if u is not None:  # (S - 1, K, 2, N, [B]) -> (S - 1, K, 2, B, N)
+                if u.numel() != s1 * k * 2 * n * b or tuple(u.shape[:3]) != (s1, k, 2):
+                    raise ValueError(f'smooth: "ffbs-mh" with mcmc_steps={k} takes a smoothing tape of shape (S - 1, K, 2, N, [B]) = '
+                                     f"({s1}, {k}, 2, {n}{', %d' % b if self._batched else ''}), got {tuple(u.shape)} (set_smoothing_tape)")
+                u = u.to(device=x_hist.device, dtype=x_hist.dtype).reshape(s1, k, 2, n, b).permute(0, 1, 2, 4, 3).contiguous()
+            out, _ = ops.smooth_mh(ctx.kind, ctx.params, x_hist, w_hist, anc_hist, ops.to_cols(idx).to(torch.int32).contiguous(), u,
+                                   self._next_draw_seed(), k)
+            return torch.stack([ops.from_soa(o, self._batched, self._has_event) for o in out.unbind(0)], 0)
         start = batched_gather(x_last, idx, 0)
         if has_kernel and (route == "kernel" or not matrix):
             x_hist, w_hist, _ = self._history(states)

@@ -86,7 +86,8 @@ class RandomWalk:
 class GradientBasedProposal(RandomWalk):
     """The gradient-informed proposal of PMMH (``proposals/gradient.py:35-97``): theta* ~ N(u + eps grad S(theta), scale) with
     ``eps = scale^2 / 2``, ``u`` the chain's current unconstrained value and ``S`` the log-likelihood plus the log prior.
-    ``grad S`` is estimated by Fisher's identity: the filter's recorded states are smoothed (``method``: ``"ffbs"`` or ``"fl"``),
+    ``grad S`` is estimated by Fisher's identity: the filter's recorded states are smoothed (``method``: ``"ffbs"``, ``"fl"`` or
+    ``"ffbs-mh"`` - the latter with ``mcmc_steps`` Metropolis-Hastings moves per backward step, see ``ParticleFilter.smooth``),
     the complete-data log-likelihood of the trajectories is differentiated (``ParticleFilter.path_score``: one HIP launch for
     the built-in models) and the gradient of ``theta.eval_priors(constrained=False)`` is added.
 
@@ -104,7 +105,7 @@ class GradientBasedProposal(RandomWalk):
     The filter must record all its states (``record_states=True``), as the reference asserts.  ``exchange`` is ``RandomWalk``'s:
     after an accepted move the chain takes over the kernel built at the accepted value."""
 
-    def __init__(self, scale=1e-2, method: str = "ffbs", use_second_order: bool = False, route: str = "auto"):
+    def __init__(self, scale=1e-2, method: str = "ffbs", use_second_order: bool = False, route: str = "auto", mcmc_steps: int = 8):
         if use_second_order:
             raise NotImplementedError("Currently does not support `use_second_order`!")
         if route not in ("auto", "kernel", "torch"):
@@ -113,6 +114,7 @@ class GradientBasedProposal(RandomWalk):
         self._eps = scale ** 2.0 / 2.0
         self._method = method
         self._route = route
+        self._mcmc_steps = int(mcmc_steps)
 
     def build(self, theta, state, filter_, y):
         states = state.filter_state.states
@@ -123,7 +125,7 @@ class GradientBasedProposal(RandomWalk):
         if isinstance(filter_, ParticleFilter):
             gen = torch.Generator(device=states[-1].timeseries_state.value.device)
             gen.manual_seed((filter_._seed * 0x9E3779B1 + filter_._draws) & 0x7FFFFFFFFFFFFFFF)
-            paths = filter_.smooth(states, self._method, generator=gen, route=self._route)
+            paths = filter_.smooth(states, self._method, generator=gen, route=self._route, mcmc_steps=self._mcmc_steps)
         else:
             paths = filter_.smooth(states, self._method)
         names = theta.names()

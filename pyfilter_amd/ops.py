@@ -535,13 +535,13 @@ def debug_draw_normals(seed: int, steps: int, n: int, b: int, d: int, dtype, dev
 
 TRACE_LEN = 2048  # launch records the library keeps per thread (PF_TRACE_LEN)
 # the entry point a record's SPEC names (csrc/pf_linear_smooth.hpp: PF_TRACE_*); every other SPEC is a launch of pf_filter_run
-TRACE_ENTRY = {20: "pf_smooth_ffbs_linear", 21: "pf_path_score_linear"}
+TRACE_ENTRY = {20: "pf_smooth_ffbs_linear", 21: "pf_path_score_linear", 22: "pf_smooth_mh"}  # (22: csrc/pf_smooth_mh.hpp)
 
 
 def debug_launch_trace(last: int = 64):
     """The step-kernel instantiations of this thread's latest fused launches, oldest first, as dicts (pf_debug_launch_trace_fields;
-    ``LEAF``: the launch took the one-column leaf of the step kernel).  ``pf_smooth_ffbs_linear`` and ``pf_path_score_linear``
-    leave one record per call too; ``ENTRY`` names the entry point a record belongs to (``TRACE_ENTRY``, else ``pf_filter_run``)."""
+    ``LEAF``: the launch took the one-column leaf of the step kernel).  ``pf_smooth_ffbs_linear``, ``pf_path_score_linear`` and
+    ``pf_smooth_mh`` leave one record per call too; ``ENTRY`` names the entry point a record belongs to (``TRACE_ENTRY``, else ``pf_filter_run``)."""
     buf = (C.c_int32 * (len(TRACE_FIELDS) * last))()
     n = L.load().pf_debug_launch_trace_fields(buf, last, len(TRACE_FIELDS))
     if n < 0:
@@ -874,3 +874,42 @@ def smooth_ffbs_linear(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hi
                                            seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), s, n, b, L.dtype_code(x_hist.dtype),
                                            L.stream_ptr()), "pf_smooth_ffbs_linear")
     return out
+
+
+def smooth_mh(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hist: torch.Tensor, anc_hist: torch.Tensor, idx_last: torch.Tensor,
+              u: Optional[torch.Tensor], seed: int, mcmc_steps: int):
+    """Backward simulation by Metropolis-Hastings over ``x_hist (S, D, B, N)`` / ``logw_hist (S, B, N)`` / ``anc_hist (S, B, N)``
+    int32 from the resampled indices ``idx_last (B, N)`` int32 of the last state (pf_smooth_mh, ``csrc/pf_smooth_mh.hpp``): every
+    trajectory starts its state-t index at the parent of its state-(t + 1) particle and makes ``mcmc_steps`` independence-sampler
+    moves - O(N K) per step.  ``u (S - 1, K, 2, B, N)`` (``[t][r][0]`` proposes, ``[t][r][1]`` accepts) or None (Philox, stream 10).
+    Built-in kinds (``D <= 3``) and the ``PF_HID_LINEAR_MAT`` kind (``D, O <= 8``).  Returns ``(out (S, D, B, N), idx_out (S, B, N)
+    int32)``: ``out[t]`` is ``x_hist[t]`` at ``idx_out[t]``."""
+    L.require_gpu(x_hist, logw_hist, anc_hist, idx_last, u, params)
+    s, d, b, n = x_hist.shape
+    k = int(mcmc_steps)
+    assert logw_hist.shape == (s, b, n) and logw_hist.dtype == x_hist.dtype
+    assert anc_hist.shape == (s, b, n) and anc_hist.dtype == torch.int32 and idx_last.shape == (b, n) and idx_last.dtype == torch.int32
+    assert x_hist.is_contiguous() and logw_hist.is_contiguous() and anc_hist.is_contiguous() and idx_last.is_contiguous()
+    assert params.is_contiguous() and params.dtype == x_hist.dtype
+    o = int(kind.obs_dim)
+    np_row = (d * d + 2 * d if kind.hid_kind == L.HID_LINEAR_MAT else 4 * d) + o * d + 2 * o
+    if int(kind.dim) != d or params.numel() != b * np_row:  # (the kernel sizes its reads by the kind)
+        raise L.PfAmdError(f"smooth_mh: history {tuple(x_hist.shape)} / rows {tuple(params.shape)} do not match the model kind")
+    if k < 0:
+        raise L.PfAmdError(f"smooth_mh: mcmc_steps must be >= 0, got {mcmc_steps}")
+    if u is not None:
+        u = u.to(x_hist.dtype).contiguous()
+        assert u.shape == (max(s - 1, 0), k, 2, b, n), (tuple(u.shape), (s - 1, k, 2, b, n))
+        if u.numel() == 0:
+            u = None
+    lib = L.load()
+    nbytes = C.c_size_t(0)
+    L.check(lib.pf_smooth_mh_workspace_bytes(n, b, s, C.byref(nbytes)), "pf_smooth_mh_workspace_bytes")
+    ws = torch.empty(max(nbytes.value, 8), dtype=torch.uint8, device=x_hist.device)
+    out = torch.empty_like(x_hist)
+    idx_out = torch.empty((s, b, n), dtype=torch.int32, device=x_hist.device)
+    m = make_model_struct(kind, params)
+    L.check(lib.pf_smooth_mh(C.byref(m), x_hist.data_ptr(), logw_hist.data_ptr(), anc_hist.data_ptr(), idx_last.data_ptr(), L.ptr(u),
+                             seed & 0xFFFFFFFFFFFFFFFF, k, out.data_ptr(), idx_out.data_ptr(), s, n, b, L.dtype_code(x_hist.dtype),
+                             ws.data_ptr(), nbytes.value, L.stream_ptr()), "pf_smooth_mh")
+    return out, idx_out
