@@ -30,8 +30,6 @@
 
 namespace pf {
 
-#define PF_STREAM_FORECAST_Z 8  // (6, 7: pf_nested.hpp)
-#define PF_STREAM_FORECAST_E 9
 #define PF_FC_ITEMS 4  // consecutive particles per thread
 #define PF_FC_TILE (PF_BLOCK * PF_FC_ITEMS)
 
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_part(ModelDesc md, const 
     __shared__ double red[Q * PF_NWAVES];
     const int b = blockIdx.y, tiles = gridDim.x;
     const int O = md.obs_dim;
-    const int NP = 4 * D + O * D + 2 * O;
+    const int NP = PF_BUILTIN_ROW_LEN(D, O);
     ColParams<T, D> cp;
     cp.load(params + (int64_t)b * NP, O, nullptr);  // (no observation: its entries are 0 and nothing here reads them)
     ColConsts<T, D> cc;
@@ -216,7 +214,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_final(ModelDesc md, const
     if (threadIdx.x == 0) {
         const int64_t hb = (int64_t)h * B + b;
         ColParams<T, D> cp;
-        cp.load(params + (int64_t)b * (4 * D + O * D + 2 * O), O, nullptr);
+        cp.load(params + (int64_t)b * PF_BUILTIN_ROW_LEN(D, O), O, nullptr);
         ColConsts<T, D> cc;
         cc.prepare(md, cp);
         // (a pivot that differed from k_forecast_part's in its last bit would move the mean by that bit and the variance not at

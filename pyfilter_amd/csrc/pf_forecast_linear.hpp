@@ -106,7 +106,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_linmat_part(const T* __re
     __shared__ double red[QA * PF_NWAVES];
     __shared__ T pvx[D], pvk[MAXO];  // the pivot of the current step: kept by the first thread, read by everyone (not in registers)
     const int b = blockIdx.y, tiles = gridDim.x;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     lin_prepare<T, D>(lc, wk, params + (int64_t)b * NP, O, nullptr, false, false);
     const int64_t plane = (int64_t)B * N;
     const int64_t i0 = ((int64_t)blockIdx.x * PF_BLOCK + threadIdx.x) * IT;
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_forecast_linmat_final(const T* __r
     __shared__ double red[PF_NWAVES];
     __shared__ LinFcFinal fin;
     const int h = blockIdx.x, b = blockIdx.y;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     lin_prepare<T, D>(lc, wk, params + (int64_t)b * NP, O, nullptr, false, false);
     const int Q = linfc_q(D, O, COV);
     const int R_M = 1 + 2 * D, R_MM = R_M + O, R_P = R_MM + O;  // rows of the slab

@@ -209,7 +209,7 @@ template <typename T, int D>
 __device__ __forceinline__ void load_col_params(const FusedArgs<T>& a, int b, int step, bool with_y, ColParams<T, D>& cp,
                                                 int late = 0) {
     const int O = a.md.obs_dim;
-    const int NP = 4 * D + O * D + 2 * O;
+    const int NP = PF_BUILTIN_ROW_LEN(D, O);
     cp.load(a.params + (int64_t)b * NP + late, O,
             with_y ? a.y + ((int64_t)step * a.y_rows + (a.y_rows == 1 ? 0 : b)) * O + late : nullptr);
 }

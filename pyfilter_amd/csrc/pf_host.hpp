@@ -284,6 +284,9 @@ static inline void trace_launch(int step, int tbytes, int d, int vec, int mode, 
     r[10] = leaf;
     ++t.count;
 }
+// The entry points besides pf_filter_run that leave a record, one per call (ops.TRACE_ENTRY names them).  Their codes occupy the
+// record's SPEC field, so they must stay above every SPEC that a filter run writes (pf_step.hip: a step kernel's specialisation).
+enum { PF_TRACE_FFBS_LINEAR = 20, PF_TRACE_SCORE_LINEAR = 21, PF_TRACE_SMOOTH_MH = 22 };
 
 // the launch arguments every fused kernel shares, from the C ABI's argument block
 template <typename T>

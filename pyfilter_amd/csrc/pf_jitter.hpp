@@ -13,8 +13,6 @@
 
 namespace pf {
 
-#define PF_JITTER_STREAM 0x4A495454u  // Philox stream word of the jitter draws ("JITT"): apart from the filters' streams 0..3
-
 // sorted order of the LDS sort: ascending values, NaN last, equal values in the order of their index - the order of a STABLE
 // sort, so that the weights of tied values accumulate in one defined order (the quartile pick reads the running sum)
 __device__ __forceinline__ bool jitter_before(double a, int ia, double b, int ib) {
@@ -192,7 +190,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_jitter_apply(ThetaPriors pr, const
     const T* eps = reinterpret_cast<const T*>(dr.eps);
     const T* sel = reinterpret_cast<const T*>(dr.select);
     auto philox = [&](uint32_t q) {
-        return philox4x32_10((uint32_t)i, q, (uint32_t)dr.counter, PF_JITTER_STREAM ^ (uint32_t)(dr.counter >> 32), (uint32_t)dr.seed,
+        return philox4x32_10((uint32_t)i, q, (uint32_t)dr.counter, PF_STREAM_JITTER ^ (uint32_t)(dr.counter >> 32), (uint32_t)dr.seed,
                              (uint32_t)(dr.seed >> 32));
     };
     double s = 1.0;

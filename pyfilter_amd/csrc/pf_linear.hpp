@@ -20,6 +20,14 @@
 
 namespace pf {
 
+// The parameter row [A | b | s | A_o | b_o | s_o]: its length, and where each block after A starts (macros: pf_models.hpp's note)
+#define PF_LINMAT_ROW_LEN(D, O) ((D) * (D) + 2 * (D) + (O) * (D) + 2 * (O))
+#define PF_LINMAT_B_AT(D) ((D) * (D))
+#define PF_LINMAT_S_AT(D) ((D) * (D) + (D))
+#define PF_LINMAT_AO_AT(D) ((D) * (D) + 2 * (D))
+#define PF_LINMAT_BO_AT(D, O) ((D) * (D) + 2 * (D) + (O) * (D))
+#define PF_LINMAT_SO_AT(D, O) ((D) * (D) + 2 * (D) + (O) * (D) + (O))
+
 // per-filter constants of the arithmetic type, as the per-particle loop reads them (LDS, broadcast reads)
 template <typename T> struct LinConsts {
     T A[PF_LIN_MAXD * PF_LIN_MAXD];   // transition matrix, row-major D x D
@@ -74,16 +82,16 @@ template <typename T, int D>
 __device__ __forceinline__ void lin_prepare(LinConsts<T>& lc, LinWork& w, const T* __restrict__ row, int O, const T* __restrict__ yrow,
                                    bool lgo, bool pre) {
     const int tid = threadIdx.x;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
-    const T* ao = row + D * D + 2 * D;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
+    const T* ao = row + PF_LINMAT_AO_AT(D);  // the observation block [A_o | b_o | s_o] from its own start
     if (tid < NP) {  // (NP <= 64 + 16 + 64 + 16 < PF_BLOCK)
         const double v = (double)row[tid];
-        if (tid < D * D) w.A[tid] = v;
-        else if (tid < D * D + D) w.b[tid - D * D] = v;
-        else if (tid < D * D + 2 * D) w.s[tid - D * D - D] = v;
-        else if (tid < D * D + 2 * D + O * D) w.Ao[tid - D * D - 2 * D] = v;
-        else if (tid < D * D + 2 * D + O * D + O) w.bo[tid - D * D - 2 * D - O * D] = v;
-        else w.so[tid - D * D - 2 * D - O * D - O] = v;
+        if (tid < PF_LINMAT_B_AT(D)) w.A[tid] = v;
+        else if (tid < PF_LINMAT_S_AT(D)) w.b[tid - PF_LINMAT_B_AT(D)] = v;
+        else if (tid < PF_LINMAT_AO_AT(D)) w.s[tid - PF_LINMAT_S_AT(D)] = v;
+        else if (tid < PF_LINMAT_BO_AT(D, O)) w.Ao[tid - PF_LINMAT_AO_AT(D)] = v;
+        else if (tid < PF_LINMAT_SO_AT(D, O)) w.bo[tid - PF_LINMAT_AO_AT(D) - O * D] = v;
+        else w.so[tid - PF_LINMAT_AO_AT(D) - O * D - O] = v;
     }
     __syncthreads();
     if (tid < O) w.yb[tid] = yrow ? (double)yrow[tid] - (double)ao[O * D + tid] : 0.0;
@@ -221,7 +229,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_linmat_sample_and_weight(const T* 
     __shared__ LinConsts<T> lc;
     __shared__ LinWork wk;
     const int b = blockIdx.y;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     const bool lgo = weigh && proposal == PF_PROP_LGO;  // (weigh = 0: propagate only, from the dynamics)
     lin_prepare<T, D>(lc, wk, params + (int64_t)b * NP, O, (weigh && y) ? y + (int64_t)(y_rows == 1 ? 0 : b) * O : nullptr, lgo, false);
     const int64_t plane = (int64_t)B * N;
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_linmat_pre_weight(const T* __restr
     __shared__ LinConsts<T> lc;
     __shared__ LinWork wk;
     const int b = blockIdx.y;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     const bool lgo = proposal == PF_PROP_LGO;
     lin_prepare<T, D>(lc, wk, params + (int64_t)b * NP, O, y + (int64_t)(y_rows == 1 ? 0 : b) * O, false, lgo);
     const int64_t plane = (int64_t)B * N;

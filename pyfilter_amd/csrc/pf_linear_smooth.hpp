@@ -3,7 +3,7 @@
 // x' = b + A x + s e with a full D x D matrix, y ~ N(b_o + A_o x, diag(s_o^2)), 1 <= D, O <= 8, parameter row
 // [A D*D | b D | s D | A_o O*D | b_o O | s_o O] (include/pf_amd.h), one row per filter.
 //
-// k_ffbs_linmat is k_ffbs' scheme (pf_kernels.hip) with this kind's candidate: one thread per trajectory for the whole backward
+// k_ffbs_linmat is k_ffbs' scheme (pf_smooth.hpp) with this kind's candidate: one thread per trajectory for the whole backward
 // pass, the workgroup stages 256 candidates - loc_i = b + A x_t^i and the sanitised log-weight - in LDS and every thread scans
 // the tiles twice, (max, sum exp) and then the inverse-CDF walk with one uniform per (trajectory, step).  s is constant per
 // filter: 1 / (2 s_d^2) is a per-filter register value, and -sum log s_d - D log sqrt(2 pi), the same for every candidate, is
@@ -29,14 +29,6 @@
 
 namespace pf {
 
-#ifndef PF_STREAM_SMOOTH
-#define PF_STREAM_SMOOTH 5
-#endif
-
-// records of the launch trace (pf_debug_launch_trace) the two entry points of this kind leave: field SPEC
-#define PF_TRACE_FFBS_LINEAR 20
-#define PF_TRACE_SCORE_LINEAR 21
-
 template <typename T, int D>
 __global__ __launch_bounds__(PF_BLOCK) void k_ffbs_linmat(const T* __restrict__ params, int O, const T* __restrict__ x_hist,
                                                            const T* __restrict__ logw_hist, const T* __restrict__ x_last,
@@ -44,14 +36,14 @@ __global__ __launch_bounds__(PF_BLOCK) void k_ffbs_linmat(const T* __restrict__ 
                                                            int64_t N, int B) {
     __shared__ T s_loc[D][PF_BLOCK], s_c[PF_BLOCK], s_A[D * D], s_b[D];
     const int b = blockIdx.y;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     const T* row = params + (int64_t)b * NP;
     if (threadIdx.x < D * D) s_A[threadIdx.x] = row[threadIdx.x];
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + D) s_b[threadIdx.x - 64] = row[D * D + threadIdx.x - 64];
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + D) s_b[threadIdx.x - 64] = row[PF_LINMAT_B_AT(D) + threadIdx.x - 64];
     T i2[D];  // 1 / (2 s_d^2)
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        const T sd = row[D * D + D + d];
+        const T sd = row[PF_LINMAT_S_AT(D) + d];
         i2[d] = T(0.5) / (sd * sd);
     }
     const int64_t plane = (int64_t)B * N;
@@ -164,11 +156,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_score_linmat_part(const T* __restr
     const bool obs = g >= gt;              // (uniform over the workgroup)
     const int r0 = (obs ? g - gt : g) * R;  // the group's first row
     const int lim = obs ? O : D;
-    const int NP = D * D + 2 * D + O * D + 2 * O;
+    const int NP = PF_LINMAT_ROW_LEN(D, O);
     const T* row = params + (int64_t)b * NP;
-    const T* mrow = obs ? row + D * D + 2 * D : row;                    // the matrix the rows come from
-    const T* orow = obs ? row + D * D + 2 * D + O * D : row + D * D;    // ... their offsets
-    const T* srow = orow + lim;                                         // ... their scales
+    const T* mrow = obs ? row + PF_LINMAT_AO_AT(D) : row;                             // the matrix the rows come from
+    const T* orow = obs ? row + PF_LINMAT_AO_AT(D) + O * D : row + PF_LINMAT_B_AT(D);  // ... their offsets (b_o behind A_o)
+    const T* srow = orow + lim;                                                       // ... their scales
 
     double M[R][D], off[R], isc[R], lg[R];
     bool act[R];
@@ -290,16 +282,16 @@ __global__ __launch_bounds__(PF_BLOCK) void k_score_linmat_final(const double* _
     } else {
         // slot k of the row [A D*D | b D | s D | A_o O*D | b_o O | s_o O] -> (row of its block, column: 0 .. D - 1, D = offset, D + 1 = scale)
         int k = q - 1, base = 0, rr, c;
-        if (k >= D * D + 2 * D) {
-            k -= D * D + 2 * D;
+        if (k >= PF_LINMAT_AO_AT(D)) {
+            k -= PF_LINMAT_AO_AT(D);  // (the observation block [A_o | b_o | s_o] from its own start)
             base = gt;
             if (k < O * D) { rr = k / D; c = k % D; }
             else if (k < O * D + O) { rr = k - O * D; c = D; }
             else { rr = k - O * D - O; c = D + 1; }
         } else {
-            if (k < D * D) { rr = k / D; c = k % D; }
-            else if (k < D * D + D) { rr = k - D * D; c = D; }
-            else { rr = k - D * D - D; c = D + 1; }
+            if (k < PF_LINMAT_B_AT(D)) { rr = k / D; c = k % D; }
+            else if (k < PF_LINMAT_S_AT(D)) { rr = k - PF_LINMAT_B_AT(D); c = D; }
+            else { rr = k - PF_LINMAT_S_AT(D); c = D + 1; }
         }
         const int g = base + rr / R, l = 1 + (rr % R) * (D + 2) + c;
         const double* row = part + ((int64_t)g * Q + l) * stride + (int64_t)b * parts;

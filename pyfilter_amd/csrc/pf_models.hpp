@@ -25,6 +25,14 @@ template <int D> struct ObsDim {
 
 // Per-column parameter row, layout (in units of T):
 //   [ hp0[D] hp1[D] hp2[D] hp3[D] | A[O*D] (row-major O x D) | ob[O] | os[O] ]       NP = 4*D + O*D + 2*O
+// The row's length and where A, ob and os start: the one statement of this layout in the library's sources (ops.row_len is
+// Python's).  Macros, not constexpr functions: a function's body is simplified on its own before it is inlined - D (O + 4) + 2 O,
+// without the no-signed-wrap flags - and the kernels' address arithmetic then compiles to other, if equivalent, instructions.
+#define PF_BUILTIN_ROW_LEN(D, O) (4 * (D) + (O) * (D) + 2 * (O))
+#define PF_BUILTIN_AO_AT(D) (4 * (D))
+#define PF_BUILTIN_BO_AT(D, O) (4 * (D) + (O) * (D))
+#define PF_BUILTIN_SO_AT(D, O) (4 * (D) + (O) * (D) + (O))
+
 template <typename T, int D> struct ColParams {
     static constexpr int MAXO = ObsDim<D>::MAXO;
     T hp[4][D];
@@ -41,7 +49,7 @@ template <typename T, int D> struct ColParams {
         for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int d = 0; d < D; ++d) hp[k][d] = row[k * D + d];
-        const T* a = row + 4 * D;
+        const T* a = row + PF_BUILTIN_AO_AT(D);  // the observation block [A | ob | os] from its own start
 #pragma unroll
         for (int o = 0; o < MAXO; ++o) {
             const bool on = o < O_;

@@ -20,11 +20,9 @@
 
 namespace pf {
 
-// Philox streams of the nested proposal (0 .. 3: pf_philox.hpp; 5: the backward smoother; "JITT": pf_jitter.hpp):
+// Philox streams of the nested proposal (pf_philox.hpp):
 //   normals   (seed, PF_STREAM_NESTED_Z, step, (b N + i) M + j)   - candidate j of particle i of filter b
 //   the pick  (seed, PF_STREAM_NESTED_PICK, step, b N + i)
-#define PF_STREAM_NESTED_Z 6
-#define PF_STREAM_NESTED_PICK 7
 
 // What a particle's M candidates share: the one-step mean and the transition scale of its parent.
 template <typename T, int D> struct NestedParent {
@@ -108,7 +106,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_nested_sample_and_weight(ModelDesc
                                                                        int32_t* __restrict__ pick_out, int64_t N, int B) {
     const int b = blockIdx.y;
     const int O = md.obs_dim;
-    const int NP = 4 * D + O * D + 2 * O;
+    const int NP = PF_BUILTIN_ROW_LEN(D, O);
     ColParams<T, D> cp;
     cp.load(params + (int64_t)b * NP, O, y + (int64_t)(y_rows == 1 ? 0 : b) * O);
     ColConsts<T, D> cc;

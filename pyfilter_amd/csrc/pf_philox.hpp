@@ -44,8 +44,34 @@ __device__ __forceinline__ Philox4 philox4x32_10_vkey(uint32_t c0, uint32_t c1, 
     return philox4x32_10(c0, c1, c2, c3, v0, v1);
 }
 
-// streams
-enum { PF_STREAM_NORMAL = 0, PF_STREAM_UNIFORM = 1, PF_STREAM_INIT = 2, PF_STREAM_MULTINOMIAL = 3 };
+// Stream words: EVERY stream of the library is defined here and nowhere else - two draws that shared a word would be correlated
+// without anything failing (tests/test_philox_cpu.py reads this enum).  What each one addresses:
+//   NORMAL       the filters' propagation normals: normal number (b N + i) D + d at counter step t
+//   UNIFORM      the systematic resampler's one uniform per column: element b at step t
+//   INIT         the initial sample: up to 4 normals of element b N + i, the counter step being the draw's group
+//   MULTINOMIAL  the multinomial resampler: uniform of element e, or - with 0x200 ORed into the word - its Exp(1) spacings
+//   SMOOTH       backward simulation (k_ffbs, k_ffbs_linmat): ONE uniform per (trajectory, step) - element b N + j at step t
+//   NESTED_Z     the nested proposal's candidates: normal (b N + i) M + j - candidate j of particle i of filter b
+//   NESTED_PICK  ... and its pick: the uniform of element b N + i
+//   FORECAST_Z   forecasting, state noise: normal number (b N + i) D + d at counter step h (the horizon step)
+//   FORECAST_E   ... observation noise, drawn only when y paths are stored: normal number (b N + i) O + o (PF_LIN_MAXO + o for
+//                PF_HID_LINEAR_MAT)
+//   SMOOTH_MH    backward simulation by Metropolis-Hastings: one call per round, call number (b N + j) K + r at step t
+//   JITTER       the jitter draws of NESS ("JITT"; pf_jitter.hpp), XORed with the high half of the update counter: every other
+//                word stays below 2^16, so no update count that a run reaches brings it onto one of them
+enum : uint32_t {
+    PF_STREAM_NORMAL = 0,
+    PF_STREAM_UNIFORM = 1,
+    PF_STREAM_INIT = 2,
+    PF_STREAM_MULTINOMIAL = 3,
+    PF_STREAM_SMOOTH = 5,
+    PF_STREAM_NESTED_Z = 6,
+    PF_STREAM_NESTED_PICK = 7,
+    PF_STREAM_FORECAST_Z = 8,
+    PF_STREAM_FORECAST_E = 9,
+    PF_STREAM_SMOOTH_MH = 10,
+    PF_STREAM_JITTER = 0x4A495454u,
+};
 
 // uniform in (0, 1]: never 0 so log() is safe
 __device__ __forceinline__ float u01_open0(uint32_t a) { return ((float)(a >> 8) + 1.0f) * (1.0f / 16777216.0f); }

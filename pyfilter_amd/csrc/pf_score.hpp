@@ -60,7 +60,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_score_part(ModelDesc md, const T* 
     __shared__ double red[Q * PF_NWAVES];
     const int b = blockIdx.y;
     const int O = md.obs_dim;
-    const int NP = 4 * D + O * D + 2 * O;
+    const int NP = PF_BUILTIN_ROW_LEN(D, O);
     const bool sv = md.obs_kind == PF_OBS_SV;
     const int kind = md.hid_kind;
     const double dt = md.dt, inc = md.inc_scale;
@@ -77,9 +77,9 @@ __global__ __launch_bounds__(PF_BLOCK) void k_score_part(ModelDesc md, const T* 
     for (int o = 0; o < MAXO; ++o) {
         const bool on = o < O;
 #pragma unroll
-        for (int d = 0; d < D; ++d) A[o][d] = on ? (double)row[4 * D + o * D + d] : 0.0;
-        ob[o] = on ? (double)row[4 * D + O * D + o] : 0.0;
-        os[o] = on ? (double)row[4 * D + O * D + O + o] : 1.0;
+        for (int d = 0; d < D; ++d) A[o][d] = on ? (double)row[PF_BUILTIN_AO_AT(D) + o * D + d] : 0.0;
+        ob[o] = on ? (double)row[PF_BUILTIN_BO_AT(D, O) + o] : 0.0;
+        os[o] = on ? (double)row[PF_BUILTIN_SO_AT(D, O) + o] : 1.0;
     }
     // Ornstein-Uhlenbeck: what depends on the parameters alone - e^{-kappa dt}, sqrt v with v = (1 - e^{-2 kappa dt}) / (2 kappa),
     // d sqrt v / d kappa = (2 kappa dt e^{-2 kappa dt} - (1 - e^{-2 kappa dt})) / (2 kappa^2) / (2 sqrt v)

@@ -2,7 +2,7 @@
 // joint smoothing distribution using Markov chain Monte Carlo"): the O(N K) way between "fl" (ancestor tracing, K = 0) and "ffbs"
 // (k_ffbs / k_ffbs_linmat: every trajectory scans all N candidates twice per step, K -> inf).
 //
-// Per filter column b and trajectory j over a history of S states (layouts of pf_kernels.hip's smoothing section):
+// Per filter column b and trajectory j over a history of S states (layouts of pf_smooth.hpp):
 //   k_{S-1} = idx_last[b][j], out[S-1][j] = x_hist[S-1][k_{S-1}];
 //   for t = S-2 .. 0, with x+ = out[t+1][j]:
 //     start  i = anc_hist[t+1][b][k_{t+1}], l = l_t(i) - or -inf when the candidate's sanitised log-weight is -inf;
@@ -23,17 +23,13 @@
 // log-density.  A chain of dependent loads: latency-bound, hidden by the N B lanes in flight.
 //
 // Draws: tape u (S - 1, K, 2, B, N) in T - [t][r][0] proposes, [t][r][1] accepts - or Philox: one call per round, call number
-// (b N + j) K + r of (seed, stream 10, step t); float: u1 = u01(word 0), u2 = u01(word 1); double: u01_d(words 0, 1), u01_d(words 2, 3).
+// (b N + j) K + r of (seed, PF_STREAM_SMOOTH_MH, step t); float: u1 = u01(word 0), u2 = u01(word 1); double: u01_d(words 0, 1), u01_d(words 2, 3).
 #pragma once
+#include "pf_linear.hpp"
 #include "pf_models.hpp"
 #include "pf_philox.hpp"
 
 namespace pf {
-
-// the Philox stream word of this method's draws (0 - 3: pf_philox.hpp, 5: PF_STREAM_SMOOTH, 6 - 9: pf_nested.hpp, pf_forecast.hpp)
-#define PF_SMOOTH_MH_STREAM 10
-// record of the launch trace (pf_debug_launch_trace) pf_smooth_mh leaves: field SPEC (20, 21: pf_linear_smooth.hpp)
-#define PF_TRACE_SMOOTH_MH 22
 
 // a recorded log-weight as a backward draw takes it: NaN, +inf, -inf and the dtype's lowest finite value are -inf (no mass)
 template <typename T> __device__ __forceinline__ T smooth_mh_logw(T v) {
@@ -99,17 +95,17 @@ __global__ __launch_bounds__(PF_BLOCK) void k_smooth_mh(ModelDesc md, const T* _
     ColParams<T, DP> cp;
     T i2[D];  // MAT: 1 / (2 s_d^2)
     if constexpr (MAT) {
-        const T* row = params + (int64_t)b * (D * D + 2 * D + O * D + 2 * O);
+        const T* row = params + (int64_t)b * PF_LINMAT_ROW_LEN(D, O);
         if (threadIdx.x < D * D) s_A[threadIdx.x] = row[threadIdx.x];
-        if (threadIdx.x >= 64 && threadIdx.x < 64 + D) s_b[threadIdx.x - 64] = row[D * D + threadIdx.x - 64];
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + D) s_b[threadIdx.x - 64] = row[PF_LINMAT_B_AT(D) + threadIdx.x - 64];
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const T sd = row[D * D + D + d];
+            const T sd = row[PF_LINMAT_S_AT(D) + d];
             i2[d] = T(0.5) / (sd * sd);
         }
         __syncthreads();
     } else {
-        cp.load(params + (int64_t)b * (4 * D + O * D + 2 * O), O, nullptr);
+        cp.load(params + (int64_t)b * PF_BUILTIN_ROW_LEN(D, O), O, nullptr);
     }
     const T inc = (T)md.inc_scale;
     const int64_t plane = (int64_t)B * N, col = (int64_t)b * N;
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_smooth_mh(ModelDesc md, const T* _
                 u2 = ur[plane];
             } else {
                 const uint64_t c = (uint64_t)(col + j) * (uint64_t)K + (uint64_t)r;
-                const Philox4 w = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)t, PF_SMOOTH_MH_STREAM, (uint32_t)seed,
+                const Philox4 w = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)t, PF_STREAM_SMOOTH_MH, (uint32_t)seed,
                                                 (uint32_t)(seed >> 32));
                 if constexpr (sizeof(T) == 4) {
                     u1 = u01(w.x);

@@ -294,6 +294,13 @@ def make_model_struct(kind, params: torch.Tensor) -> L.PfModel:
     return m
 
 
+def row_len(kind) -> int:
+    """Values in one parameter row of ``kind`` (``pf_model.params``; csrc: ``builtin_row_len`` / ``linmat_row_len``):
+    ``[hp0[D] hp1[D] hp2[D] hp3[D] | A[OxD] | b[O] | s[O]]``, or ``[A[DxD] | b[D] | s[D] | A[OxD] | b[O] | s[O]]`` for ``PF_HID_LINEAR_MAT``."""
+    d, o = int(kind.dim), int(kind.obs_dim)
+    return (d * d + 2 * d if kind.hid_kind == L.HID_LINEAR_MAT else 4 * d) + o * d + 2 * o
+
+
 def _y_rows(y: torch.Tensor, b: int, obs_dim: int) -> Tuple[torch.Tensor, int]:
     """Canonical ``(rows, O)`` device layout of one observation: rows = 1 (shared) or B (one series per filter)."""
     yy = y.reshape(-1, obs_dim) if y.numel() != obs_dim else y.reshape(1, obs_dim)
@@ -407,7 +414,7 @@ def forecast_linear_soa(kind, params, steps: int, x: torch.Tensor, W: Optional[t
     o, steps = int(kind.obs_dim), int(steps)
     dt, dev = x.dtype, x.device
     assert x.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
-    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+    if int(kind.dim) != d or params.shape[1] != row_len(kind):  # (the kernel sizes its reads and writes by the kind)
         raise L.PfAmdError(f"forecast_linear_soa: state {tuple(x.shape)} / rows {tuple(params.shape)} do not match the model kind")
     if W is not None:
         assert tuple(W.shape) == (b, n) and W.is_contiguous() and W.dtype == dt
@@ -445,7 +452,7 @@ def path_score(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: torch.Ten
     o = int(kind.obs_dim)
     dt, dev = paths_soa.dtype, paths_soa.device
     assert paths_soa.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
-    if int(kind.dim) != d or params.shape[1] != 4 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+    if int(kind.dim) != d or params.shape[1] != row_len(kind):  # (the kernel sizes its reads and writes by the kind)
         raise L.PfAmdError(f"path_score: paths {tuple(paths_soa.shape)} / rows {tuple(params.shape)} do not match the model kind")
     yy = y.to(device=dev, dtype=dt).reshape(s - 1, -1, o).contiguous() if s >= 2 else torch.zeros((1, 1, o), dtype=dt, device=dev)
     rows = yy.shape[1]
@@ -472,7 +479,7 @@ def path_score_linear(kind, params: torch.Tensor, paths_soa: torch.Tensor, y: to
     o = int(kind.obs_dim)
     dt, dev = paths_soa.dtype, paths_soa.device
     assert paths_soa.is_contiguous() and params.is_contiguous() and params.dtype == dt and params.shape[0] == b
-    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads and writes by the kind)
+    if int(kind.dim) != d or params.shape[1] != row_len(kind):  # (the kernel sizes its reads and writes by the kind)
         raise L.PfAmdError(f"path_score_linear: paths {tuple(paths_soa.shape)} / rows {tuple(params.shape)} do not match the model kind")
     yy = y.to(device=dev, dtype=dt).reshape(s - 1, -1, o).contiguous() if s >= 2 else torch.zeros((1, 1, o), dtype=dt, device=dev)
     rows = yy.shape[1]
@@ -534,8 +541,8 @@ def debug_draw_normals(seed: int, steps: int, n: int, b: int, d: int, dtype, dev
 
 
 TRACE_LEN = 2048  # launch records the library keeps per thread (PF_TRACE_LEN)
-# the entry point a record's SPEC names (csrc/pf_linear_smooth.hpp: PF_TRACE_*); every other SPEC is a launch of pf_filter_run
-TRACE_ENTRY = {20: "pf_smooth_ffbs_linear", 21: "pf_path_score_linear", 22: "pf_smooth_mh"}  # (22: csrc/pf_smooth_mh.hpp)
+# the entry point a record's SPEC names (the PF_TRACE_* enum of csrc/pf_host.hpp); every other SPEC is a launch of pf_filter_run
+TRACE_ENTRY = {20: "pf_smooth_ffbs_linear", 21: "pf_path_score_linear", 22: "pf_smooth_mh"}
 
 
 def debug_launch_trace(last: int = 64):
@@ -862,8 +869,7 @@ def smooth_ffbs_linear(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hi
     assert logw_hist.shape == (s, b, n) and x_last.shape == (d, b, n)
     assert x_hist.is_contiguous() and logw_hist.is_contiguous() and x_last.is_contiguous()
     assert params.is_contiguous() and params.dtype == x_hist.dtype and params.shape[0] == b
-    o = int(kind.obs_dim)
-    if int(kind.dim) != d or params.shape[1] != d * d + 2 * d + o * d + 2 * o:  # (the kernel sizes its reads by the kind)
+    if int(kind.dim) != d or params.shape[1] != row_len(kind):  # (the kernel sizes its reads by the kind)
         raise L.PfAmdError(f"smooth_ffbs_linear: history {tuple(x_hist.shape)} / rows {tuple(params.shape)} do not match the model kind")
     if u is not None:
         u = u.to(x_hist.dtype).contiguous()
@@ -891,9 +897,7 @@ def smooth_mh(kind, params: torch.Tensor, x_hist: torch.Tensor, logw_hist: torch
     assert anc_hist.shape == (s, b, n) and anc_hist.dtype == torch.int32 and idx_last.shape == (b, n) and idx_last.dtype == torch.int32
     assert x_hist.is_contiguous() and logw_hist.is_contiguous() and anc_hist.is_contiguous() and idx_last.is_contiguous()
     assert params.is_contiguous() and params.dtype == x_hist.dtype
-    o = int(kind.obs_dim)
-    np_row = (d * d + 2 * d if kind.hid_kind == L.HID_LINEAR_MAT else 4 * d) + o * d + 2 * o
-    if int(kind.dim) != d or params.numel() != b * np_row:  # (the kernel sizes its reads by the kind)
+    if int(kind.dim) != d or params.numel() != b * row_len(kind):  # (the kernel sizes its reads by the kind)
         raise L.PfAmdError(f"smooth_mh: history {tuple(x_hist.shape)} / rows {tuple(params.shape)} do not match the model kind")
     if k < 0:
         raise L.PfAmdError(f"smooth_mh: mcmc_steps must be >= 0, got {mcmc_steps}")

@@ -31,6 +31,7 @@ import torch
 from torch.distributions import Distribution, Independent, Normal
 
 from .. import _lib as L
+from .. import ops
 from . import AffineProcess, KernelKind, StateSpaceModel, TimeseriesState, _as_tensor
 
 
@@ -302,4 +303,6 @@ def pack_params(ssm: StateSpaceModel, b: int, dtype, device) -> torch.Tensor:
         cols.append(torch.zeros((b, o * d), dtype=dtype, device=device))
         cols.append(_expand(mu, b, (o,), dtype, device))
         cols.append(torch.ones((b, o), dtype=dtype, device=device))
-    return torch.cat([c.reshape(b, -1) for c in cols], dim=1).contiguous()
+    rows = torch.cat([c.reshape(b, -1) for c in cols], dim=1).contiguous()
+    assert rows.shape[1] == ops.row_len(kind)  # (what the host checks and the kernels take a row to hold)
+    return rows

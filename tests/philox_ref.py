@@ -27,7 +27,8 @@ _WEYL_A, _WEYL_B = 0x9E3779B9, 0xBB67AE85  # golden ratio, sqrt(3) - 1
 ROUNDS = 10
 
 # the stream words of the library (tests/test_philox_cpu.py checks them against the sources)
-STREAMS = dict(NORMAL=0, UNIFORM=1, INIT=2, MULTINOMIAL=3, SMOOTH=5, NESTED_Z=6, NESTED_PICK=7, FORECAST_Z=8, FORECAST_E=9)
+STREAMS = dict(NORMAL=0, UNIFORM=1, INIT=2, MULTINOMIAL=3, SMOOTH=5, NESTED_Z=6, NESTED_PICK=7, FORECAST_Z=8, FORECAST_E=9,
+               SMOOTH_MH=10, JITTER=0x4A495454)
 EXP_FLAG = 0x200  # ORed into the stream word of the Exp(1) spacings
 
 

@@ -133,6 +133,48 @@ def test_pack_params_layout():
         models.pack_params(ts.StateSpaceModel(ts.AffineProcess(lambda x, s: (x.value, s), (t(1.0),), None, None), None, ()), 1, torch.float32, "cpu")
 
 
+@pytest.mark.parametrize("d,o", [(1, 1), (3, 3), (1, 2)])
+@pytest.mark.parametrize("obs_kind", ["linear", "sv"])
+def test_row_len_is_what_pack_params_packs_builtin(obs_kind, d, o):
+    """``ops.row_len`` (the host checks' number) against the packer and against the layout written out HERE - the independent copy:
+    ``[hp0[D] hp1[D] hp2[D] hp3[D] | A[O x D] | b[O] | s[O]]``.  The kinds are built directly: these are shapes of the row, not
+    all of them shapes a public model class has."""
+    from types import SimpleNamespace
+
+    from pyfilter_amd import _lib as L
+    from pyfilter_amd import ops
+    from pyfilter_amd.timeseries import KernelKind, models
+
+    kind = KernelKind(L.HID_LINEAR, d, 1.0, 1.0)
+    kind.obs_kind, kind.obs_dim = (L.OBS_LINEAR, o) if obs_kind == "linear" else (L.OBS_SV, o)
+    hidden = SimpleNamespace(parameters=(torch.zeros(d), torch.full((d,), 0.9), torch.full((d,), 0.1)))
+    obs = (torch.ones(o, d), torch.zeros(o), torch.ones(o)) if obs_kind == "linear" else (torch.zeros(o),)
+    ssm = SimpleNamespace(kernel_kind=kind, hidden=hidden, parameters=obs, n_dim=1)
+    rows = models.pack_params(ssm, 4, torch.float64, "cpu")  # (a batch that is none of the D and O: no (B,) parameter is ambiguous)
+    assert rows.shape[1] == ops.row_len(kind) == 4 * d + o * d + 2 * o
+
+
+@pytest.mark.parametrize("d,o", [(1, 1), (8, 8), (5, 3), (3, 5)])
+def test_row_len_is_what_pack_params_packs_linear_matrix(d, o):
+    """... for ``PF_HID_LINEAR_MAT``, ``[A[D x D] | b[D] | s[D] | A_o[O x D] | b_o[O] | s_o[O]]``: O < D and O > D are where a swapped
+    ``O * D`` would show."""
+    from torch.distributions import Independent, Normal
+
+    from pyfilter_amd import _lib as L
+    from pyfilter_amd import ops
+    from pyfilter_amd import timeseries as ts
+    from pyfilter_amd.timeseries import LinearModel, models
+
+    f64 = torch.float64
+    inc = Independent(Normal(torch.zeros(d, dtype=f64), torch.ones(d, dtype=f64)), 1)
+    hidden = LinearModel((torch.eye(d, dtype=f64), torch.zeros(d, dtype=f64), torch.ones(d, dtype=f64)), inc, lambda *_: inc)
+    ssm = ts.LinearStateSpaceModel(hidden, (torch.ones(o, d, dtype=f64), torch.zeros(o, dtype=f64), torch.ones(o, dtype=f64)), torch.Size([o]))
+    kind = ssm.kernel_kind
+    assert (kind.hid_kind, kind.dim, kind.obs_dim) == (L.HID_LINEAR_MAT, d, o)
+    rows = models.pack_params(ssm, 2, f64, "cpu")
+    assert rows.shape[1] == ops.row_len(kind) == d * d + 2 * d + o * d + 2 * o
+
+
 def test_layout_views_round_trip_without_copies():
     from pyfilter_amd import ops
 

@@ -15,6 +15,7 @@ from oracle import cpu_ref
 from oracle.cases import build_spec
 from tests import philox_cases as PC
 from tests import philox_ref as P
+from tests.source_registries import streams_in_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pyfilter_amd", "csrc")
@@ -55,22 +56,10 @@ def test_word_to_number():
 
 
 # ---- stream words ------------------------------------------------------------------------------------------------------------
-def _streams_in_sources():
-    found = {}
-    for name in sorted(os.listdir(CSRC)):
-        with open(os.path.join(CSRC, name)) as f:
-            text = f.read()
-        pairs = re.findall(r"#define\s+PF_STREAM_(\w+)\s+(\d+)", text)
-        for body in re.findall(r"enum\s*\{([^}]*PF_STREAM_[^}]*)\}", text):
-            pairs += re.findall(r"PF_STREAM_(\w+)\s*=\s*(\d+)", body)
-        for key, val in pairs:
-            assert found.setdefault(key, int(val)) == int(val), f"PF_STREAM_{key} defined twice with different values"
-    return found
-
-
 def test_stream_words_are_those_of_the_sources_and_distinct():
-    src = _streams_in_sources()
-    assert src == P.STREAMS, (src, P.STREAMS)
+    """The one enum of ``pf_philox.hpp`` (a ``PF_STREAM_*`` defined anywhere else fails the parse) against ``philox_ref.STREAMS``."""
+    src = streams_in_sources()
+    assert src == P.STREAMS and len(src) == 11, (src, P.STREAMS)
     with open(os.path.join(CSRC, "pf_philox.hpp")) as f:
         flags = set(re.findall(r"stream \| (0x[0-9a-fA-F]+)u", f.read()))
     assert flags == {hex(P.EXP_FLAG)}, flags

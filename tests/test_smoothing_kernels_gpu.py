@@ -1,4 +1,4 @@
-"""The two smoothing kernels of ``csrc/pf_kernels.hip`` called directly - ``k_ffbs`` (``pf_smooth_ffbs``) and ``k_trace_ancestors``
+"""The two smoothing kernels of ``csrc/pf_smooth.hpp`` called directly - ``k_ffbs`` (``pf_smooth_ffbs``) and ``k_trace_ancestors``
 (``pf_smooth_fixed_lag``) - against the float64 oracle, in both dtypes, on every built-in kind and at the shapes and weight edges
 the kernels have code for (inputs and bars: ``tests/smoothing_cases.py``).
 

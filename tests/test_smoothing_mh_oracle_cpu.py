@@ -13,6 +13,7 @@ from tests import philox_ref as P
 from tests import smoothing_cases as sc
 from tests import smoothing_mh_oracle as mh
 from tests.helpers import DT
+from tests.source_registries import streams_in_sources, trace_codes_in_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,12 +30,14 @@ def test_entry_points_are_declared():
         header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     assert re.search(r"int pf_smooth_mh\(const pf_model\* model,", header) and "int pf_smooth_mh_workspace_bytes(" in header
     assert "#define PF_ABI_VERSION 4" in header and _lib.ABI_VERSION == 4
-    assert ops.TRACE_ENTRY[22] == "pf_smooth_mh"
-    with open(os.path.join(ROOT, "pyfilter_amd", "csrc", "pf_smooth_mh.hpp")) as f:
-        source = f.read()
-    assert re.search(r"#define\s+PF_TRACE_SMOOTH_MH\s+22\b", source)
-    stream = int(re.search(r"#define\s+PF_SMOOTH_MH_STREAM\s+(\d+)", source).group(1))
-    assert stream == 10 and stream not in P.STREAMS.values() and stream != (P.STREAMS["MULTINOMIAL"] | P.EXP_FLAG)
+    codes = trace_codes_in_sources()
+    assert codes == {"FFBS_LINEAR": 20, "SCORE_LINEAR": 21, "SMOOTH_MH": 22}
+    assert ops.TRACE_ENTRY == {codes["FFBS_LINEAR"]: "pf_smooth_ffbs_linear", codes["SCORE_LINEAR"]: "pf_path_score_linear",
+                               codes["SMOOTH_MH"]: "pf_smooth_mh"}
+    streams = streams_in_sources()
+    stream = streams.pop("SMOOTH_MH")
+    assert stream == 10 == mh.PHILOX_STREAM == P.STREAMS["SMOOTH_MH"]
+    assert stream not in streams.values() and stream != (streams["MULTINOMIAL"] | P.EXP_FLAG)
     with open(os.path.join(ROOT, "pyfilter_amd", "csrc", "pf_kernels.hip")) as f:
         assert '#include "pf_smooth_mh.hpp"' in f.read()
 

@@ -23,10 +23,10 @@ from tests import philox_ref as PR
 from tests import theta_cases as TC
 from tests import theta_oracle as O
 from tests.ness_replay import CONSTANT_SCALE, NESS_CASES
+from tests.source_registries import streams_in_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-CSRC = os.path.join(ROOT, "pyfilter_amd", "csrc")
 RTOL, ATOL = 1e-8, 1e-10  # tests/replay.py::close
 THETA_RTOL, THETA_ATOL = 1e-11, 1e-12  # the project's theta bar (tests/test_theta_kernels_gpu.py::_tol)
 OU = ((O.EXPONENTIAL, 10.0, 0.0), (O.NORMAL, 0.0, 1.0), (O.LOGNORMAL, -2.0, 1.0))  # kappa, gamma, sigma: tests/ness_replay.py::priors
@@ -340,15 +340,8 @@ def test_product_fit_and_resampling_agree_with_the_oracle(b, p, pattern):
 
 
 # ---- the jitter kernels' addresses ----------------------------------------------------------------------------------------------
-def _jitter_stream_in_sources():
-    with open(os.path.join(CSRC, "pf_jitter.hpp")) as f:
-        found = re.findall(r"#define\s+PF_JITTER_STREAM\s+(0x[0-9A-Fa-f]+)u", f.read())
-    assert len(found) == 1, found
-    return int(found[0], 16)
-
-
 def test_jitter_stream_word_is_the_one_of_the_sources():
-    assert _jitter_stream_in_sources() == O.JITTER_STREAM == int.from_bytes(b"JITT", "big")
+    assert streams_in_sources()["JITTER"] == PR.STREAMS["JITTER"] == O.JITTER_STREAM == int.from_bytes(b"JITT", "big")
 
 
 def test_jitter_addresses_are_injective_and_apart_from_the_filter_streams():
@@ -365,8 +358,9 @@ def test_jitter_addresses_are_injective_and_apart_from_the_filter_streams():
     rows = np.concatenate(rows)
     assert (rows < 2 ** 32).all()
     assert len(np.unique(rows, axis=0)) == len(rows) == 4 * 9 * 8192
-    theirs = set(PR.STREAMS.values()) | {PR.STREAMS["MULTINOMIAL"] | PR.EXP_FLAG}
-    assert max(theirs) < 2 ** 16 and O.JITTER_STREAM not in theirs
+    others = {name: word for name, word in PR.STREAMS.items() if name != "JITTER"}  # (test_philox_cpu.py: all the sources define)
+    theirs = set(others.values()) | {others["MULTINOMIAL"] | PR.EXP_FLAG}
+    assert len(others) == len(PR.STREAMS) - 1 == 10 and max(theirs) < 2 ** 16 and O.JITTER_STREAM not in theirs
     low = rows[rows[:, 3] == O.JITTER_STREAM]
     assert len(low) == 3 * 9 * 8192  # (every counter below 2^32 carries the bare stream word)
     # the draws themselves: unit-variance normals, uniforms below `prob` at the rate `prob`, two updates apart
